@@ -10,18 +10,27 @@ A step = one END-TO-END compaction job: the timed region covers the input
 SST file reads (tmpfs), H2D staging, the full GPU pipeline, plan FSM, D2H
 and output file writes — everything the reference CPU worker's hot loop
 pays (its input reads are inside the timed path, table/block_fetcher.cc:242).
-A secondary `hbm_resident` figure (inputs staged in HBM before the region)
-is reported alongside, never as `value`.
 
-`cpu_baseline` runs the CPU oracle worker on ALL host cores (one job per
-core, jobs-in-parallel — the production dcompact worker's own concurrency
-model) over a bounded sample of the same 8-way workload shape; the
-single-core figure is reported next to it.
+A plain run does only what the headline figure needs: generate the inputs,
+warm up, time the K steps, print the result line.  The kernel table and the
+roofline object come from HIP events the timed steps record anyway.
+
+`--full` adds the legs that take runs of their own:
+- `hbm_resident`: a second timed region with the inputs staged in HBM
+  before it; reported alongside, never as `value`.
+- `cpu_baseline`: the CPU oracle worker on ALL host cores (one job per
+  core, jobs-in-parallel — the production dcompact worker's own concurrency
+  model) over a bounded sample of the same 8-way workload shape; the
+  single-core figure is reported next to it.
+
+`--dump-outputs DIR` writes what the last timed step produced (the output
+SSTs and the job result a caller of dcw_execute receives) as DIR/<name>.npy
+so two builds can be compared output for output; see dump_outputs().
 
 Weak scaling: each rank owns independent jobs (distinct seeds) — compaction
 jobs share nothing; no data-path collective.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 (driver launches N>1 via torch.distributed.run; RANK/LOCAL_RANK read from
 the env; barriers over the default process group.)
 """
@@ -128,6 +137,86 @@ def load_pmc_traffic(kernel):
         return None
 
 
+DUMP_CHUNK = 4096          # bytes per digest row
+DUMP_SAMPLE = 8 << 20      # sampled SST bytes (float32 -> 32 MiB on disk)
+DUMP_SEED = 0x64637721
+
+
+def dump_outputs(out_dir, last, suffix=""):
+    """Write what the last timed step returned to its caller as
+    <out_dir>/<name><suffix>.npy (float32/float64, < 64 MB in all):
+
+      job_counts        [in_bytes, out_bytes, in_entries, out_entries]
+      file_meta         per output file: size, num_entries, smallest_seqno,
+                        largest_seqno, len(smallest ikey), len(largest ikey)
+      file_smallest_key / file_largest_key
+                        per file, the ikey bytes padded with -1 to 64 (or
+                        to the longest key, if one is longer)
+      sst_chunk_digest  over the output SSTs concatenated in result order,
+                        per 4 KiB chunk: [byte sum, sum of byte*(1 + i%16)]
+                        (both exact) — covers every output byte
+      sst_bytes_sample  the bytes at a fixed seeded set of offsets of that
+                        concatenation (all of it when it is small)
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+
+    files = last["files"]
+    save("job_counts", np.array([last["in_bytes"], last["out_bytes"],
+                                 last["in_entries"], last["out_entries"]],
+                                dtype=np.float64))
+    save("file_meta", np.array(
+        [[f["file_size"], f["num_entries"], f["smallest_seqno"],
+          f["largest_seqno"], len(f["smallest"]), len(f["largest"])]
+         for f in files], dtype=np.float64).reshape(len(files), 6))
+    for name, key in (("file_smallest_key", "smallest"),
+                      ("file_largest_key", "largest")):
+        width = max([64] + [len(f[key]) for f in files])
+        a = np.full((len(files), width), -1.0, dtype=np.float32)
+        for i, f in enumerate(files):
+            a[i, :len(f[key])] = np.frombuffer(f[key], dtype=np.uint8)
+        save(name, a)
+
+    blobs = [np.fromfile(f["path"], dtype=np.uint8) for f in files]
+    sizes = [len(b) for b in blobs]
+    total = sum(sizes)
+    weights = (np.arange(DUMP_CHUNK) % 16 + 1).astype(np.float32)
+    digest = []
+    carry = np.zeros(0, dtype=np.uint8)
+    for bi, b in enumerate(blobs):  # chunks run across file boundaries
+        b = np.concatenate([carry, b]) if len(carry) else b
+        n_full = len(b) // DUMP_CHUNK * DUMP_CHUNK
+        if bi == len(blobs) - 1 and n_full < len(b):
+            b = np.concatenate(
+                [b, np.zeros(n_full + DUMP_CHUNK - len(b), dtype=np.uint8)])
+            n_full += DUMP_CHUNK
+        rows = b[:n_full].reshape(-1, DUMP_CHUNK)
+        carry = b[n_full:]
+        d = np.empty((len(rows), 2), dtype=np.float64)
+        d[:, 0] = rows.sum(axis=1, dtype=np.uint64)
+        # float32 is exact here: every partial sum < 255*16*4096 < 2^24
+        d[:, 1] = rows.astype(np.float32) @ weights
+        digest.append(d)
+    save("sst_chunk_digest",
+         np.concatenate(digest) if digest else np.zeros((0, 2)))
+
+    if total <= DUMP_SAMPLE:
+        sample = (np.concatenate(blobs) if blobs
+                  else np.zeros(0, dtype=np.uint8)).astype(np.float32)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(
+            0, total, size=DUMP_SAMPLE))
+        sample = np.empty(DUMP_SAMPLE, dtype=np.float32)
+        starts = np.cumsum([0] + sizes)
+        for b, s0, s1 in zip(blobs, starts[:-1], starts[1:]):
+            lo, hi = np.searchsorted(pos, [s0, s1])
+            sample[lo:hi] = b[pos[lo:hi] - s0]
+    save("sst_bytes_sample", sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -138,9 +227,17 @@ def main():
                     help="~64 MiB snappy SST per run at 16B/100B")
     ap.add_argument("--compression", type=int, default=1, help="0=none 1=snappy")
     ap.add_argument("--workdir", default="/dev/shm/dcw_bench")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: "
+                         "the all-core CPU baseline and the hbm_resident "
+                         "staged-inputs region (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baseline")
     ap.add_argument("--skip-hbm-resident", action="store_true",
-                    help="skip the secondary staged-inputs region")
+                    help="with --full: leave out the staged-inputs region")
     ap.add_argument("--table-factory", choices=["bbt", "dzt"], default="bbt",
                     help="dzt = DcwZipTable searchable-compressed output "
                          "(BASELINE configs[3]); bbt = BlockBasedTable")
@@ -194,9 +291,9 @@ def main():
         (rank, len(runs), in_bytes / 2**20, time.time() - t_gen))
 
     # CPU baseline before GPU init (forked children must not inherit a live
-    # HIP context); rank 0 at N=1 only
+    # HIP context); rank 0 at N=1 only, --full only
     cpu_base = None
-    if rank == 0 and world == 1 and not args.skip_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.skip_cpu_baseline:
         t0 = time.time()
         cpu_base = cpu_baseline(args, work, dcw, rank)
         log("cpu_baseline: %.1f MB/s on %d cores (single core %.1f) in %.1fs"
@@ -359,9 +456,17 @@ def main():
             "ms_per_launch": round(per_launch_ms, 4),
         }
 
-    # ---- SECONDARY: inputs already resident in HBM (staged) ----
+    # the last timed step's outputs, before anything else reuses the slots
+    if args.dump_outputs and last is not None:
+        t0 = time.time()
+        dump_outputs(args.dump_outputs, last,
+                     suffix="" if rank == 0 else "_r%d" % rank)
+        log("rank %d: dumped outputs to %s in %.1fs" %
+            (rank, args.dump_outputs, time.time() - t0))
+
+    # ---- SECONDARY (--full): inputs already resident in HBM (staged) ----
     hbm_resident = None
-    if not args.skip_hbm_resident and my_queue_jobs is None:
+    if args.full and not args.skip_hbm_resident and my_queue_jobs is None:
         handle = dcw.stage_inputs(job(0))
         run_steps(max(2, jif // 2), staged=handle)  # short re-warm
         e2, _ = timed(args.steps, staged=handle)
