@@ -325,13 +325,49 @@ def default_table_opts(**kw) -> TableOpts:
     return t
 
 
-def build_sst(entries, opts: TableOpts = None, tombstones=()) -> bytes:
+_CODECCB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t,
+                       C.POINTER(C.c_uint8),
+                       C.POINTER(C.POINTER(C.c_uint8)),
+                       C.POINTER(C.c_size_t))
+_lib.orc_table_builder_set_data_block_codec.argtypes = [
+    C.c_void_p, _CODECCB, C.c_void_p]
+
+
+def build_sst(entries, opts: TableOpts = None, tombstones=(),
+              data_block_codec=None) -> bytes:
     """entries: iterable of (internal_key: bytes, value: bytes), sorted.
     tombstones: iterable of (start_ukey, end_ukey, seq) -> the
-    "rocksdb.range_del" meta block."""
+    "rocksdb.range_del" meta block.
+    data_block_codec: optional callable(raw_block: bytes) -> None (store the
+    block raw) or (compression_type: int, payload: bytes), consulted for data
+    blocks only; the payload is stored as given under a valid trailer
+    checksum (tests build foreign-encoder inputs with it)."""
     if opts is None:
         opts = default_table_opts()
     b = _lib.orc_table_builder_new(C.byref(opts))
+    codec_err = []
+    if data_block_codec is not None:
+        keep = [None]  # payload of the latest call; C reads it before the next
+
+        @_CODECCB
+        def cb(_arg, raw, n, type_out, out, outn):
+            try:
+                r = data_block_codec(C.string_at(raw, n))
+                if r is None:
+                    return 0
+                ctype, payload = r
+                buf = (C.c_uint8 * max(len(payload), 1)).from_buffer_copy(
+                    bytes(payload) or b"\0")
+                keep[0] = buf
+                type_out[0] = ctype
+                out[0] = C.cast(buf, C.POINTER(C.c_uint8))
+                outn[0] = len(payload)
+                return 1
+            except Exception as e:  # noqa: BLE001 — re-raised after finish
+                codec_err.append(e)
+                return 0
+
+        _lib.orc_table_builder_set_data_block_codec(b, cb, None)
     for k, v in entries:
         _lib.orc_table_builder_add(b, k, len(k), v, len(v))
     for st, en, seq in tombstones:
@@ -341,6 +377,8 @@ def build_sst(entries, opts: TableOpts = None, tombstones=()) -> bytes:
     data = C.string_at(out.data, out.size)
     _lib.orc_buf_free(C.byref(out))
     _lib.orc_table_builder_delete(b)
+    if codec_err:
+        raise codec_err[0]
     return data
 
 

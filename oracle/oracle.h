@@ -101,6 +101,18 @@ typedef struct orc_table_builder orc_table_builder;
 orc_table_builder* orc_table_builder_new(const orc_table_opts* o);
 void orc_table_builder_add(orc_table_builder* b, const uint8_t* ikey,
                            size_t klen, const uint8_t* value, size_t vlen);
+/* Optional data-block codec hook (TEST INFRASTRUCTURE: lets tests build
+ * inputs whose data blocks a foreign encoder wrote).  Consulted for DATA
+ * blocks only; index, filter and meta blocks are untouched.  Receives the
+ * raw block; returns 0 = store raw (type 0), or non-zero with *type and
+ * (*out,*outn) set: the payload is stored as given (no GoodCompressionRatio
+ * check) and the trailer checksum is computed over it.  *out must stay
+ * valid until the next callback or the builder's finish. */
+typedef int (*orc_block_codec_cb)(void* arg, const uint8_t* raw, size_t n,
+                                  uint8_t* type, const uint8_t** out,
+                                  size_t* outn);
+void orc_table_builder_set_data_block_codec(orc_table_builder* b,
+                                            orc_block_codec_cb cb, void* arg);
 /* estimated file size = bytes written so far (BlockBasedTableBuilder::FileSize) */
 uint64_t orc_table_builder_file_size(const orc_table_builder* b);
 uint64_t orc_table_builder_num_entries(const orc_table_builder* b);

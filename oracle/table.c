@@ -197,7 +197,16 @@ struct orc_table_builder {
   uint64_t raw_key_size, raw_value_size, num_data_blocks, data_size, index_size;
   uint64_t tail_start_offset;
   orc_buf scratch, scratch2, comp;
+  /* optional data-block codec hook (tests build foreign-encoder inputs) */
+  orc_block_codec_cb codec;
+  void* codec_arg;
 };
+
+void orc_table_builder_set_data_block_codec(orc_table_builder* b,
+                                            orc_block_codec_cb cb, void* arg) {
+  b->codec = cb;
+  b->codec_arg = arg;
+}
 
 void orc_table_opts_default(orc_table_opts* o) {
   memset(o, 0, sizeof(*o));
@@ -255,12 +264,24 @@ extern size_t ZSTD_compress(void*, size_t, const void*, size_t, int);
 extern size_t ZSTD_decompress(void*, size_t, const void*, size_t);
 extern unsigned ZSTD_isError(size_t);
 
+#define TB_DATA_BLOCK 2 /* try_compress value: compressible AND a data block */
 static void tb_write_block(orc_table_builder* b, const uint8_t* data, size_t n,
                            int try_compress, uint64_t* hoff, uint64_t* hsize) {
   uint8_t type = DCW_COMPRESSION_NONE;
   const uint8_t* out = data;
   size_t outn = n;
-  if (try_compress && b->o.compression == DCW_COMPRESSION_ZSTD) {
+  if (try_compress == TB_DATA_BLOCK && b->codec) {
+    /* hook decides: raw, or (type, payload) stored as given — no
+     * GoodCompressionRatio check; the trailer checksum covers the payload */
+    uint8_t ctype = DCW_COMPRESSION_NONE;
+    const uint8_t* cout = NULL;
+    size_t coutn = 0;
+    if (b->codec(b->codec_arg, data, n, &ctype, &cout, &coutn)) {
+      type = ctype;
+      out = cout;
+      outn = coutn;
+    }
+  } else if (try_compress && b->o.compression == DCW_COMPRESSION_ZSTD) {
     /* ZSTD_Compress framing (util/compression.h:1332-1377): varint32
      * decompressed size + zstd frame, level 3 (kDefaultCompressionLevel) */
     buf_reserve(&b->comp, ZSTD_compressBound(n) + 8);
@@ -387,7 +408,8 @@ static void tb_flush_data(orc_table_builder* b) {
   orc_buf* s = &b->scratch;
   oblk_finish(&b->data, s);
   oblk_reset(&b->data);
-  tb_write_block(b, s->data, s->size, 1, &b->pending_off, &b->pending_size);
+  tb_write_block(b, s->data, s->size, TB_DATA_BLOCK, &b->pending_off,
+                 &b->pending_size);
   b->data_size = b->file.size; /* block_based_table_builder.cc:1130 */
   b->num_data_blocks++;
   b->has_pending = 1;

@@ -7,12 +7,34 @@
 #include <random>
 #define __device__
 #define __forceinline__ inline
-#include "/tmp/snap_dec_body.inc"
+#ifndef SNAP_DEC_BODY // extract.py's output; -DSNAP_DEC_BODY='"<path>"' to move it
+#define SNAP_DEC_BODY "/tmp/snap_dec_body.inc"
+#endif
+#include SNAP_DEC_BODY
 extern "C" {
   size_t orc_snappy_compress(const uint8_t*, size_t, uint8_t*);
   size_t orc_snappy_uncompress(const uint8_t*, size_t, uint8_t*, size_t);
 }
+// 4-byte literal lengths near 2^32 once wrapped the 32-bit bounds checks
+// (len, ip + len, op + len) and were accepted; every decoder must refuse
+static int wrap_cases(){
+  static const uint32_t lm1s[] = {0xffffffffu, 0xfffffffau, 0xffffff00u, 0x80000000u};
+  for (uint32_t lm1 : lm1s) {
+    std::vector<uint8_t> s = {100, 9 << 2, 0,1,2,3,4,5,6,7,8,9, 63 << 2,
+      (uint8_t)lm1, (uint8_t)(lm1 >> 8), (uint8_t)(lm1 >> 16), (uint8_t)(lm1 >> 24)};
+    uint32_t n = (uint32_t)s.size() + 20; // 20 payload bytes follow the header
+    s.resize(n + 16, 0xab);
+    std::vector<uint8_t> o(100 + 16), r(100 + 1);
+    if (orc_snappy_uncompress(s.data(), n, r.data(), 100) != 0 ||
+        snap_dec_lds_host(s.data(), n, o.data(), 100) != 0 ||
+        snap_dec_lds_host0(s.data(), n, o.data(), 100) != 0) {
+      printf("WRAP ACCEPTED lm1=%08x\n", lm1); return 1;
+    }
+  }
+  return 0;
+}
 int main(){
+  if (wrap_cases()) return 1;
   std::mt19937 rng(7);
   for (int it = 0; it < 20000; it++) {
     // generate data with tunable redundancy to hit all op forms

@@ -224,7 +224,10 @@ __device__ uint32_t snap_dec_wave(const uint8_t* __restrict__ in, uint32_t n,
         if (len > 60) {
           uint32_t nb = len - 60;
           if (ip + 1 + nb > n) return 0;
-          len = (uint32_t)((h >> 8) & (0xffffffffull >> (8 * (4 - nb)))) + 1;
+          uint32_t lm1 = (uint32_t)((h >> 8) & (0xffffffffull >> (8 * (4 - nb))));
+          // a 4-byte length near 2^32 would wrap len / ip + len below
+          if (lm1 >= n) return 0;
+          len = lm1 + 1;
           hb = 1 + nb;
         }
         ip += hb;
@@ -350,7 +353,10 @@ __device__ uint32_t snap_dec_lds(const uint8_t* __restrict__ in, uint32_t n,
       if (len > 60) {
         uint32_t nb = len - 60; // 1..4 length bytes, little-endian
         if (ip + 1 + nb > n) return 0;
-        len = (uint32_t)((h >> 8) & (0xffffffffull >> (8 * (4 - nb)))) + 1;
+        uint32_t lm1 = (uint32_t)((h >> 8) & (0xffffffffull >> (8 * (4 - nb))));
+        // a 4-byte length near 2^32 would wrap len / ip + len below
+        if (lm1 >= n) return 0;
+        len = lm1 + 1;
         hb = 1 + nb;
       }
       ip += hb;
@@ -678,11 +684,14 @@ __global__ void k_count_entries(const uint8_t* __restrict__ ublob,
       if (!win_varint32(W, pos, end, &shared)) break;
       if (!win_varint32(W, pos, end, &non_shared)) break;
       if (!win_varint32(W, pos, end, &vlen)) break;
-      pos += non_shared + vlen;
-      if (pos > end) {
+      // 64-bit: a corrupt length must not wrap pos back below end (the walk
+      // would never terminate); same check as k_decode_entries
+      uint64_t nxt = (uint64_t)pos + non_shared + vlen;
+      if (nxt > end) {
         set_err(err_flag, DE_BLOCK_PARSE);
         return;
       }
+      pos = (uint32_t)nxt;
       n++;
     }
     iv_cnt[i] = n;
