@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import foreign_snappy as fs  # noqa: E402
 import oracle  # noqa: E402
 
-DEC_MAX = 4992  # dcw_kernels.hip: LDS decoders take n <= DEC_MAX, usize <= DEC_MAX
+DEC_MAX = 4992  # dcw_k_decode.h: LDS decoders take n <= DEC_MAX, usize <= DEC_MAX
 SNAPPY = 1
 TYPE_DELETION, TYPE_VALUE = 0, 1
 

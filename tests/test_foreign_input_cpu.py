@@ -332,18 +332,13 @@ needs_gxx = pytest.mark.skipif(shutil.which("g++") is None,
 
 
 def _build_host_tool(tmp_path, name):
-    """extract.py lifts snap_dec_lds out of the kernel file; `name`.cpp is
-    compiled against it (and the oracle codec).  -> executable path."""
-    inc = tmp_path / "snap_dec_body.inc"
-    if not inc.exists():
-        r = subprocess.run([sys.executable, os.path.join(TOOL, "extract.py"),
-                            str(inc)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        assert "snap_dec_lds" in inc.read_text()
+    """`name`.cpp is compiled against the kernels' own dcw_snap_dec_lds.h
+    (and the oracle codec).  -> executable path."""
     orc = os.path.join(REPO, "oracle")
     exe = tmp_path / name
     r = subprocess.run(
-        ["g++", "-O2", "-DSNAP_DEC_BODY=\"%s\"" % inc, "-o", str(exe),
+        ["g++", "-O2", "-I", os.path.join(REPO, "toplingdb_amd", "csrc"),
+         "-o", str(exe),
          os.path.join(TOOL, name + ".cpp"),
          os.path.join(orc, "liborc.so"), "-Wl,-rpath," + orc],
         capture_output=True, text=True)
@@ -353,9 +348,10 @@ def _build_host_tool(tmp_path, name):
 
 @needs_gxx
 def test_host_decoder_fuzzers_build_and_pass(tmp_path):
-    """dec_fuzz / wave_fuzz run the extracted snap_dec_lds (and a simulation
-    of snap_dec_wave) against the oracle codec.  A kernel refactor that
-    breaks the extraction or the decoders' host behaviour fails here."""
+    """dec_fuzz / wave_fuzz run the host build of snap_dec_lds (and a
+    simulation of snap_dec_wave) against the oracle codec.  A kernel refactor
+    that breaks the header's host build or the decoders' host behaviour
+    fails here."""
     for name in ("dec_fuzz", "wave_fuzz"):
         r = subprocess.run([_build_host_tool(tmp_path, name)],
                            capture_output=True, text=True, timeout=300)
@@ -365,7 +361,7 @@ def test_host_decoder_fuzzers_build_and_pass(tmp_path):
 
 @needs_gxx
 def test_kernel_decoders_on_foreign_corpus_host(tmp_path, corpus_blocks):
-    """The kernel file's own snap_dec_lds<0>/<1> source, compiled for the
+    """The kernels' own snap_dec_lds<0>/<1> source, compiled for the
     host, and the snap_dec_wave simulation decode every foreign stream of
     the corpus to the raw block and refuse every malformed stream."""
     recs = bytearray()

@@ -423,3 +423,75 @@ def test_grandparent_cuts_match_oracle(tmp_path):
         rg = dcw.execute(jd)
         ro = oracle.execute(jo)
         assert_identical(rg, ro)
+
+
+def test_device_buffers_reused_across_jobs_of_changing_size(tmp_path):
+    # One worker keeps its device buffers from job to job (grow-only).  Jobs
+    # of changing size and shape, a refused job in between and a staged
+    # execute must each see buffers that fit: every accepted job is
+    # bit-identical to the oracle, and the same tiny job gives the same
+    # bytes whatever ran before it.
+    rnd = random.Random(11)
+
+    def both(name, runs, **kw):
+        d = tmp_path / name
+        (d / "out_gpu").mkdir(parents=True)
+        (d / "out_orc").mkdir()
+        rg = dcw.execute(dcw.make_job(runs, str(d / "out_gpu"), **kw))
+        ro = oracle.execute(oracle.make_job(runs, str(d / "out_orc"), **kw))
+        assert_identical(rg, ro)
+        return [open(f["path"], "rb").read() for f in rg["files"]]
+
+    def sub(name):
+        d = tmp_path / name
+        d.mkdir()
+        return d
+
+    tiny = gen_runs(sub("in_tiny"), 2, 500, seed0=21, compression=1)
+    big = gen_runs(sub("in_big"), 2, 10000, seed0=31, compression=1)
+    first = both("tiny1", tiny, compression=1)
+    both("big", big, compression=1)
+    assert both("tiny2", tiny, compression=1) == first
+
+    # general keys: mixed user-key lengths up to 48 B
+    gk, seq = [], 1
+    for r in range(2):
+        kvs = []
+        for _ in range(1500):
+            uk = rnd.randbytes(rnd.choice([6, 10, 16, 24, 33, 48]))
+            kvs.append((uk, seq, 1, b"v%d" % seq))
+            seq += 1
+        gk.append([_write_kv_run(sub("in_gk%d" % r), "g.sst", ikey_sort(kvs))])
+    both("general", gk, bottommost_level=1, compression=1)
+
+    # snapshots (the job uploads its snapshot list to the device)
+    sn, seq = [[], []], 1
+    for k in range(600):
+        for _ in range(rnd.randrange(1, 5)):
+            t = 0 if rnd.random() < 0.25 else 1
+            sn[rnd.randrange(2)].append(
+                (b"k%014d" % k, seq, t, b"" if t == 0 else b"v%d" % seq))
+            seq += 1
+    sn = [[_write_kv_run(sub("in_sn%d" % i), "s.sst", ikey_sort(kv))]
+          for i, kv in enumerate(sn)]
+    snaps = sorted(rnd.sample(range(1, seq), 3))
+    both("snaps", sn, snapshots=snaps,
+         earliest_write_conflict_snapshot=snaps[0], bottommost_level=0)
+
+    # one corrupted data block: refused, and the worker stays usable
+    bad = gen_runs(sub("in_bad"), 2, 3000, seed0=41, compression=1)
+    blob = bytearray(open(bad[1][0], "rb").read())
+    blob[100] ^= 0xFF  # inside the first data block
+    open(bad[1][0], "wb").write(bytes(blob))
+    with pytest.raises(RuntimeError, match="input block verify failed, code 1"):
+        dcw.execute(dcw.make_job(bad, str(sub("out_bad")), compression=1))
+
+    assert both("tiny3", tiny, compression=1) == first
+
+    # staged (prefetched) execute of the same job
+    jd = dcw.make_job(tiny, str(sub("out_staged")), compression=1)
+    h = dcw.stage_inputs(jd)
+    jd.staged_handle = h
+    rs = dcw.execute(jd)
+    dcw.release_staged(h)
+    assert [open(f["path"], "rb").read() for f in rs["files"]] == first

@@ -1,5 +1,5 @@
 // Runs a file of snappy streams through the host-compiled snap_dec_lds
-// (PIPE=0 and PIPE=1, extracted from the kernel file) and the snap_dec_wave
+// (PIPE=0 and PIPE=1, from the kernels' own header) and the snap_dec_wave
 // simulation, and compares with the expected bytes.  The streams come from
 // encoders other than the project's own (tests/foreign_snappy.py), so the
 // decoders meet op forms its codec never emits before any GPU time is spent.
@@ -15,10 +15,8 @@
 #include <vector>
 #define __device__
 #define __forceinline__ inline
-#ifndef SNAP_DEC_BODY
-#define SNAP_DEC_BODY "/tmp/snap_dec_body.inc"
-#endif
-#include SNAP_DEC_BODY
+#include "dcw_snap_dec_lds.h"
+#include "dec_host.h"
 #include "wave_sim.h"
 
 typedef uint32_t (*dec_fn)(const uint8_t*, uint32_t, uint8_t*, uint32_t);

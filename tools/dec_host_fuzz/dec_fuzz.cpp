@@ -1,4 +1,5 @@
-// host-compiled copy of snap_dec_lds for fuzzing against the oracle codec
+// the kernels' snap_dec_lds, compiled for the host from its own header
+// (-I toplingdb_amd/csrc), fuzzed against the oracle codec
 #include <cstdint>
 #include <cstring>
 #include <cstdio>
@@ -7,10 +8,8 @@
 #include <random>
 #define __device__
 #define __forceinline__ inline
-#ifndef SNAP_DEC_BODY // extract.py's output; -DSNAP_DEC_BODY='"<path>"' to move it
-#define SNAP_DEC_BODY "/tmp/snap_dec_body.inc"
-#endif
-#include SNAP_DEC_BODY
+#include "dcw_snap_dec_lds.h"
+#include "dec_host.h"
 extern "C" {
   size_t orc_snappy_compress(const uint8_t*, size_t, uint8_t*);
   size_t orc_snappy_uncompress(const uint8_t*, size_t, uint8_t*, size_t);

@@ -2,7 +2,8 @@
 #
 # The PRODUCT package: a GPU compaction-offload worker for ToplingDB's
 # dcompact seam (CompactionExecutor, db/compaction/compaction_executor.h).
-# The compute path is hand-written HIP for gfx950 (csrc/dcw_kernels.hip);
+# The compute path is hand-written HIP for gfx950 (csrc/dcw_gpu.hip and
+# the dcw_k_*.h kernel headers it includes);
 # this module is ctypes plumbing for tests and bench.py.  It never imports
 # the oracle.
 import ctypes as C

@@ -1,5 +1,5 @@
-// dcw_gpu.h — interface of the device pipeline (implemented in
-// dcw_kernels.hip).  The worker (dcw_worker.cpp) drives one GpuJob per
+// dcw_gpu.h — interface of the device pipeline (host runtime in
+// dcw_gpu.hip, kernels in the dcw_k_*.h headers it includes).  The worker (dcw_worker.cpp) drives one GpuJob per
 // compaction job:
 //   stage() -> decode() -> merge() -> dedup() -> [per file: plan on host,
 //   emit_blocks() -> pack_and_fetch()/block keys/gathers] -> host tail.
@@ -184,7 +184,7 @@ class GpuJob {
   // the prefix normkey + full-key side table
   bool general_keys = false;
 
-  struct Impl; // implementation detail (dcw_kernels.hip)
+  struct Impl; // implementation detail (dcw_gpu.hip)
 
  private:
   Impl* p_;

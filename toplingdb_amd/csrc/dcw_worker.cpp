@@ -5,7 +5,7 @@
 // worker lifecycle like DBImplSecondary::CompactWithoutInstallation,
 // db/db_impl/db_impl_secondary.cc:805): deserialize job -> open input SSTs
 // -> GPU hot loop (decode/merge/dedup/encode) -> write SSTs -> return file
-// metas.  The hot path runs on the GPU (dcw_kernels.hip); the host does I/O,
+// metas.  The hot path runs on the GPU (dcw_gpu.hip); the host does I/O,
 // the block/file-cut plan FSM over per-entry size metadata
 // (SURVEY.md §7 "plan pass"), and the per-file meta tail (<0.1% of bytes).
 // There is NO CPU fallback: without a GPU, dcw_init fails.
