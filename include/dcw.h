@@ -61,7 +61,12 @@ enum {
 
 /* One sorted input stream ("run"): either a single L0 file, or the ordered,
  * non-overlapping file list of one level >= 1
- * (VersionSet::MakeInputIterator, db/version_set.cc:7269-7352). */
+ * (VersionSet::MakeInputIterator, db/version_set.cc:7269-7352).
+ * Each input file may be a BlockBasedTable (format_version 5) or a
+ * DcwZipTable ("DZT1", the worker's own output_table_factory = 1 format);
+ * the kind is detected per file from its footer magic, and the two kinds
+ * may be mixed freely, across runs and inside one run.  All inputs of a job
+ * must share one checksum_type. */
 typedef struct dcw_run {
   const char* const* files; /* SST paths, in key order for level runs */
   uint32_t num_files;

@@ -20,11 +20,27 @@ struct BlockRef {
   uint32_t size; // on-disk (possibly compressed) block size
 };
 
+// One DcwZipTable ("DZT1") input file, as parse_dzt validated it.  Its
+// bytes lie in the staged blob like any other input; offsets here are
+// absolute blob offsets.  `blocks_before` places the file among the
+// BlockBasedTable blocks of its run: that many entries of
+// GpuInputs::blocks precede it in run-major file order.
+struct DztFileRef {
+  uint32_t run = 0;
+  uint32_t blocks_before = 0;
+  uint32_t ukey_len = 0, dict_size = 0;
+  uint64_t n = 0;
+  uint64_t key_off = 0, dict_off = 0, value_off = 0, kindex_off = 0;
+  std::vector<DztKeyIndexEntry> kblocks;
+  std::vector<DztValueIndexEntry> vblocks;
+};
+
 struct GpuInputs {
   const uint8_t* blob = nullptr; // pinned host buffer: input files concatenated
   size_t blob_size = 0;
   std::vector<BlockRef> blocks;         // grouped by run, run-major order
   std::vector<uint32_t> run_block_begin; // size num_runs+1
+  std::vector<DztFileRef> dzt_files;     // run-major file order
   uint32_t checksum_type = 4;
 };
 
@@ -37,6 +53,7 @@ struct StagedInput {
   uint32_t n_blocks = 0;
   uint32_t checksum_type = 4;
   std::vector<uint32_t> run_block_begin;
+  std::vector<DztFileRef> dzt_files; // host tables of the DZT files in d_blob
   ~StagedInput();
 };
 
@@ -193,6 +210,10 @@ class GpuJob {
   std::vector<uint8_t> h_shared_, h_klen_;
   std::vector<uint32_t> h_vlen_;
   std::vector<uint32_t> run_blocks_;
+  std::vector<DztFileRef> dzt_files_; // DZT inputs of the staged job
+  // DZT branch of decode(): table upload, and the key-block decode
+  int dzt_upload_tables(std::string* err);
+  int dzt_decode_keys(bool general, std::string* err);
   std::vector<RdFrag> rd_frags_;
 };
 

@@ -41,6 +41,7 @@
 #include "dcw_k_merge.h"
 #include "dcw_k_emit.h"
 #include "dcw_k_filter_dzt.h"
+#include "dcw_k_dzt_in.h"
 
 namespace dcw {
 
@@ -413,6 +414,15 @@ struct GpuJob::Impl {
   DevBuf<uint8_t> d_kext;    // general-key side table (48 B/entry full ukeys)
   DevBuf<uint32_t> d_sw;     // survivor -> original payload index
   DevBuf<uint64_t> d_flush_offs; // flush-offload record offsets
+  // DZT input path: host-built tables (dcw_k_dzt_in.h) + per-block btype
+  DevBuf<DztVbIn> d_dzi_vbs;
+  DevBuf<DztKbIn> d_dzi_kbs;
+  DevBuf<DztFileIn> d_dzi_files;
+  DevBuf<uint8_t> d_dzi_btype;
+  std::vector<DztVbIn> h_dzi_vbs;
+  std::vector<DztKbIn> h_dzi_kbs; // out_base filled once entry counts are known
+  uint64_t dzi_ulen_total = 0;    // decoded bytes of all DZT value blocks
+  uint64_t dzi_ubase = 0;         // where they start in d_ublob
   DevBuf<uint64_t> d_fhash;      // per-file filter hashes
   DevBuf<uint32_t> d_filter;     // filter bit array
   PinnedBuf h_plan; // host landing for next+meta (pageable if pinning fails)
@@ -521,6 +531,7 @@ void GpuJob::reset() {
   h_klen_.clear();
   h_vlen_.clear();
   run_blocks_.clear();
+  dzt_files_.clear();
   rd_frags_.clear();
   ms_decode = ms_merge = ms_dedup = ms_emit = ms_h2d = ms_d2h = 0;
 }
@@ -599,6 +610,7 @@ int GpuJob::stage(const GpuInputs& in, std::string* err) {
   p->staged_split = false;
   // remember run boundaries (translated to entries later)
   run_blocks_ = in.run_block_begin;
+  dzt_files_ = in.dzt_files;
   return 0;
 }
 
@@ -616,6 +628,7 @@ int GpuJob::stage_adopt(const StagedInput& s, std::string* err) {
   p->n_blocks = s.n_blocks;
   p->checksum_type = s.checksum_type;
   run_blocks_ = s.run_block_begin;
+  dzt_files_ = s.dzt_files;
   if (p->arm_consts(err) != 0) return -1;
   HIPCHK(hipStreamSynchronize(p->stream));
   return 0;
@@ -632,6 +645,7 @@ int GpuJob::stage_release(StagedInput* s, std::string* err) {
   s->n_blocks = p->n_blocks;
   s->checksum_type = p->checksum_type;
   s->run_block_begin = run_blocks_;
+  s->dzt_files = dzt_files_;
   return 0;
 }
 
@@ -642,11 +656,26 @@ int GpuJob::decode(std::string* err) {
   HIPCHK(p->d_usize.reserve(sizeof(uint32_t) * nb));
   HIPCHK(p->d_btype_in.reserve(nb));
   double in_block_bytes = 0; // filled below from bsize D2H; verify reads them
+  // DZT inputs: a second class of blocks beside the BlockBasedTable ones;
+  // each step below launches its DZT kernel right behind the existing one
+  const bool has_dzt = !dzt_files_.empty();
+  p->dzi_ulen_total = 0;
+  if (has_dzt && dzt_upload_tables(err) != 0) return -1;
+  const uint32_t n_dvb = has_dzt ? (uint32_t)p->h_dzi_vbs.size() : 0;
   p->kbegin("verify_checksum", 0);
   hipLaunchKernelGGL(k_verify_usize, dim3(grid_for(nb)), dim3(256), 0, p->stream,
                      p->d_blob, p->d_boff, p->d_bsize, nb, p->checksum_type,
                      p->d_crc, p->d_usize, p->d_btype_in, p->d_err);
   p->kend();
+  if (n_dvb) {
+    double stored = 0;
+    for (auto& v : p->h_dzi_vbs) stored += v.csize + 5.0;
+    p->kbegin("dzt_verify_vblocks", stored);
+    hipLaunchKernelGGL(k_dzt_verify_vblocks, dim3(grid_for(n_dvb, 64)),
+                       dim3(64), 0, p->stream, p->d_blob, p->d_dzi_vbs, n_dvb,
+                       p->checksum_type, p->d_crc, p->d_dzi_btype, p->d_err);
+    p->kend();
+  }
   // host scan of usize -> uoff
   std::vector<uint32_t> usize(nb);
   HIPCHK(hipMemcpyAsync(usize.data(), p->d_usize, sizeof(uint32_t) * nb,
@@ -662,7 +691,8 @@ int GpuJob::decode(std::string* err) {
   p->ublob_size = acc;
   HIPCHK(p->d_uoff.reserve(sizeof(uint64_t) * nb));
   HIPCHK(p->h2d_meta(p->d_uoff, uoff.data(), sizeof(uint64_t) * nb));
-  HIPCHK(p->d_ublob.reserve(acc ? acc : 1));
+  p->dzi_ubase = acc; // decoded DZT value blocks follow the decoded BBT blocks
+  HIPCHK(p->d_ublob.reserve(acc + p->dzi_ulen_total ? acc + p->dzi_ulen_total : 1));
   {
     std::lock_guard<std::mutex> lk(g_kmu);
     kstats()["verify_checksum"].alg_bytes += in_block_bytes;
@@ -691,6 +721,17 @@ int GpuJob::decode(std::string* err) {
                        p->d_err, dec_pipe);
   }
   p->kend();
+  if (n_dvb) {
+    double stored = 0;
+    for (auto& v : p->h_dzi_vbs) stored += v.csize;
+    p->kbegin("dzt_decompress", stored + (double)p->dzi_ulen_total);
+    // one wave (one workgroup) per value block
+    hipLaunchKernelGGL(k_dzt_decompress, dim3(n_dvb < 65536 ? n_dvb : 65536),
+                       dim3(WAVE), 0, p->stream, p->d_blob, p->d_dzi_vbs,
+                       p->d_dzi_files, p->d_dzi_btype, n_dvb,
+                       p->d_ublob.get() + p->dzi_ubase, p->d_err);
+    p->kend();
+  }
   HIPCHK(p->d_nrestarts.reserve(sizeof(uint32_t) * nb));
   hipLaunchKernelGGL(k_num_restarts, dim3(grid_for(nb)), dim3(256), 0, p->stream,
                      p->d_ublob, p->d_uoff, p->d_usize, nb, p->d_nrestarts,
@@ -744,6 +785,54 @@ int GpuJob::decode(std::string* err) {
                                                 : total_entries);
   }
   p->run_entry_begin.push_back(total_entries);
+  if (has_dzt) {
+    // a run may mix both file kinds: lay the entry ranges out again in
+    // run-major FILE order, each DZT file (n from its props) between the
+    // BlockBasedTable blocks that blocks_before names
+    std::vector<uint64_t> blk_cnt(nb, 0), blk_base(nb, 0);
+    for (uint64_t i = 0; i < niv; i++) blk_cnt[iv_block[i]] += iv_cnt[i];
+    p->run_entry_begin.clear();
+    uint64_t pos = 0;
+    size_t zi = 0, kb_row = 0;
+    auto put_blocks = [&](uint32_t b0, uint32_t b1) {
+      for (uint32_t b = b0; b < b1; b++) {
+        blk_base[b] = pos;
+        pos += blk_cnt[b];
+      }
+    };
+    for (size_t r = 0; r + 1 < run_blocks_.size(); r++) {
+      p->run_entry_begin.push_back(pos);
+      uint32_t b = run_blocks_[r];
+      for (; zi < dzt_files_.size() && dzt_files_[zi].run == r; zi++) {
+        const DztFileRef& z = dzt_files_[zi];
+        put_blocks(b, z.blocks_before);
+        b = z.blocks_before;
+        for (size_t k = 0; k < z.kblocks.size(); k++)
+          p->h_dzi_kbs[kb_row++].out_base =
+              (uint32_t)(pos + z.kblocks[k].first_rank);
+        pos += z.n;
+      }
+      put_blocks(b, run_blocks_[r + 1]);
+    }
+    p->run_entry_begin.push_back(pos);
+    if (pos > 0xfffffff0ull) {
+      if (err) *err = "too many input entries";
+      return -1;
+    }
+    uint32_t cur_blk = 0xffffffffu;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < niv; i++) {
+      if (iv_block[i] != cur_blk) {
+        cur_blk = iv_block[i];
+        at = blk_base[cur_blk];
+      }
+      iv_base[i] = (uint32_t)at;
+      at += iv_cnt[i];
+    }
+    total_entries = pos;
+    p->n_entries = total_entries;
+    n_entries_ = total_entries;
+  }
   HIPCHK(p->h2d_meta(p->d_iv_base, iv_base.data(), sizeof(uint32_t) * niv));
   HIPCHK(p->d_ent[0].reserve(sizeof(ulong4) * total_entries));
   HIPCHK(p->d_ent[1].reserve(sizeof(ulong4) * total_entries));
@@ -762,7 +851,17 @@ int GpuJob::decode(std::string* err) {
                         p->stream));
   // no message yet: DE_UKEY_LEN is not a failure but the cue to retry
   if (p->check_err(nullptr, err, &code, &t) != 0) return -1;
-  if (code == DE_UKEY_LEN) {
+  // DZT files state their key length in the props, so their mode is known
+  // before their key kernel runs (once, in the right mode): fast only when
+  // every DZT file and every BlockBasedTable entry share one U <= 16
+  bool dzt_general = false;
+  if (has_dzt) {
+    uint32_t zu = dzt_files_[0].ukey_len;
+    for (auto& z : dzt_files_) dzt_general |= z.ukey_len != zu;
+    dzt_general |= zu > 16 || (uklen != 0xffffffffu && uklen != zu);
+    if (!dzt_general) uklen = zu;
+  }
+  if (code == DE_UKEY_LEN || (code == DE_OK && dzt_general)) {
     // GENERAL-KEY retry: mixed lengths / 16 < ukey <= DCW_GKEY_MAX via the
     // prefix normkey + full-key side table (arbitrary-length bytewise
     // contract, db/dbformat.h:1057-1096)
@@ -783,13 +882,96 @@ int GpuJob::decode(std::string* err) {
     }
     general_keys = true;
     ukey_len = 0;
-    return 0;
+    return has_dzt ? dzt_decode_keys(true, err) : 0;
   }
   if (code) {
     if (err) *err = "entry decode failed, code " + std::to_string(code);
     return -1;
   }
   ukey_len = uklen;
+  return has_dzt ? dzt_decode_keys(false, err) : 0;
+}
+
+// Build the flat DZT tables from the parsed files and upload them.  Every
+// offset was bounds-checked against its section by parse_dzt.
+int GpuJob::dzt_upload_tables(std::string* err) {
+  Impl* p = p_;
+  p->h_dzi_vbs.clear();
+  p->h_dzi_kbs.clear();
+  std::vector<DztFileIn> files;
+  uint64_t uoff = 0;
+  for (size_t fi = 0; fi < dzt_files_.size(); fi++) {
+    const DztFileRef& z = dzt_files_[fi];
+    const uint32_t vb0 = (uint32_t)p->h_dzi_vbs.size();
+    for (auto& v : z.vblocks) {
+      DztVbIn row;
+      row.off = z.value_off + v.voff;
+      row.uoff = uoff;
+      row.csize = v.csize;
+      row.ulen = v.ulen;
+      row.first_rank = (uint32_t)v.first_rank;
+      row.file = (uint32_t)fi;
+      p->h_dzi_vbs.push_back(row);
+      uoff += v.ulen;
+    }
+    size_t vb = 0; // value block holding each key block's first rank
+    for (size_t k = 0; k < z.kblocks.size(); k++) {
+      const DztKeyIndexEntry& e = z.kblocks[k];
+      while (vb + 1 < z.vblocks.size() && z.vblocks[vb + 1].first_rank <= e.first_rank)
+        vb++;
+      uint64_t next = k + 1 < z.kblocks.size() ? z.kblocks[k + 1].first_rank : z.n;
+      DztKbIn row;
+      row.off = z.key_off + e.koff;
+      row.kidx_off = z.kindex_off + k * ((uint64_t)z.ukey_len + 28);
+      row.ksize = e.ksize;
+      row.count = (uint32_t)(next - e.first_rank);
+      row.first_rank = (uint32_t)e.first_rank;
+      row.out_base = 0;
+      row.vb_start = vb0 + (uint32_t)vb;
+      row.file = (uint32_t)fi;
+      row.has_next = k + 1 < z.kblocks.size();
+      row.pad = 0;
+      p->h_dzi_kbs.push_back(row);
+    }
+    DztFileIn f;
+    f.dict_off = z.dict_off;
+    f.dict_size = z.dict_size;
+    f.U = z.ukey_len;
+    f.vb_end = (uint32_t)p->h_dzi_vbs.size();
+    f.pad = 0;
+    files.push_back(f);
+  }
+  p->dzi_ulen_total = uoff;
+  size_t nvb = p->h_dzi_vbs.size();
+  HIPCHK(p->d_dzi_vbs.reserve(sizeof(DztVbIn) * nvb));
+  HIPCHK(p->d_dzi_files.reserve(sizeof(DztFileIn) * files.size()));
+  HIPCHK(p->d_dzi_btype.reserve(nvb));
+  HIPCHK(p->h2d_meta(p->d_dzi_vbs, p->h_dzi_vbs.data(), sizeof(DztVbIn) * nvb));
+  HIPCHK(p->h2d_meta(p->d_dzi_files, files.data(), sizeof(DztFileIn) * files.size()));
+  return 0;
+}
+
+// Key-block decode of every DZT file into the shared entry arrays; runs
+// behind the BlockBasedTable entry decode, in the mode decode() settled.
+int GpuJob::dzt_decode_keys(bool general, std::string* err) {
+  Impl* p = p_;
+  PhaseTimer t(p->stream, &ms_decode);
+  uint32_t nkb = (uint32_t)p->h_dzi_kbs.size();
+  HIPCHK(p->d_dzi_kbs.reserve(sizeof(DztKbIn) * nkb));
+  HIPCHK(p->h2d_meta(p->d_dzi_kbs, p->h_dzi_kbs.data(), sizeof(DztKbIn) * nkb));
+  double key_bytes = 0, ents = 0;
+  for (auto& k : p->h_dzi_kbs) {
+    key_bytes += k.ksize;
+    ents += k.count;
+  }
+  p->kbegin("dzt_decode_keys", key_bytes + (general ? 93.0 : 45.0) * ents);
+  hipLaunchKernelGGL(k_dzt_decode_keys, dim3(grid_for(nkb, 64)), dim3(64), 0,
+                     p->stream, p->d_blob, p->d_dzi_kbs, nkb, p->d_dzi_vbs,
+                     p->d_dzi_files, p->dzi_ubase, general ? 1 : 0, p->d_ent[0],
+                     p->d_voff, p->d_vlen, p->d_klen, p->d_kext, p->d_err);
+  p->kend();
+  uint32_t code = 0;
+  if (p->check_err("DZT key decode", err, &code, &t) != 0) return -1;
   return 0;
 }
 

@@ -102,6 +102,128 @@ std::string BlockBuilder::Finish() {
 extern "C" size_t ZSTD_decompress(void*, size_t, const void*, size_t);
 extern "C" unsigned ZSTD_isError(size_t);
 
+// ---------------- DZT1 input parsing (oracle/dzt.c format) ----------------
+static const uint64_t kDztMagic = 0x313050495A574344ull; // "DCWZIP01"
+static const size_t kDztFooter = 96;
+
+bool is_dzt_file(const uint8_t* data, size_t size) {
+  return size >= kDztFooter && load64(data + size - 8) == kDztMagic;
+}
+
+ParsedDzt parse_dzt(const uint8_t* data, size_t size) {
+  ParsedDzt r;
+  auto bad = [&r](const char* why) -> ParsedDzt& {
+    r.error = std::string("DZT: ") + why;
+    return r;
+  };
+  if (!is_dzt_file(data, size)) return bad("bad magic");
+  const uint8_t* f = data + size - kDztFooter;
+  const uint64_t dict_off = load64(f), value_off = load64(f + 8),
+                 kindex_off = load64(f + 16), vindex_off = load64(f + 24),
+                 props_off = load64(f + 32), props_size = load64(f + 40);
+  r.checksum_type = load32(f + 68);
+  if (load32(f + 72) != 1) return bad("unsupported version");
+  if (r.checksum_type != 0 && r.checksum_type != 1 && r.checksum_type != 4)
+    return bad("unsupported checksum_type");
+  const uint64_t body = size - kDztFooter;
+  // sections in file order, each inside the one before the footer; compared
+  // one bound at a time so no sum of two file-supplied numbers is formed
+  if (!(dict_off <= value_off && value_off <= kindex_off &&
+        kindex_off <= vindex_off && vindex_off <= props_off &&
+        props_off <= body && props_size == body - props_off))
+    return bad("footer offsets out of range");
+  const uint64_t key_size = dict_off, dict_size = value_off - dict_off,
+                 value_size = kindex_off - value_off,
+                 kindex_size = vindex_off - kindex_off,
+                 vindex_size = props_off - vindex_off;
+  const uint32_t ct = r.checksum_type;
+  auto sect_ok = [&](uint64_t off, uint64_t sz, uint32_t want) {
+    return block_checksum(ct, &g_crc, data + off, sz, 0) == want;
+  };
+  if (!sect_ok(dict_off, dict_size, load32(f + 52)))
+    return bad("dict checksum mismatch");
+  if (!sect_ok(kindex_off, kindex_size, load32(f + 56)))
+    return bad("key index checksum mismatch");
+  if (!sect_ok(vindex_off, vindex_size, load32(f + 60)))
+    return bad("value index checksum mismatch");
+  if (!sect_ok(props_off, props_size, load32(f + 64)))
+    return bad("props checksum mismatch");
+  {
+    // one checksum over the whole key area: not parallel across key blocks,
+    // so it is taken here on the host, not on the GPU
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    bool ok = sect_ok(0, key_size, load32(f + 48));
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    r.key_csum_usec = (uint64_t)((t1.tv_sec - t0.tv_sec) * 1000000LL +
+                                 (t1.tv_nsec - t0.tv_nsec) / 1000);
+    if (!ok) return bad("key area checksum mismatch");
+  }
+  if (props_size < 88) return bad("props too small");
+  const uint8_t* pr = data + props_off;
+  r.n = load64(pr);
+  const uint64_t n_kblocks = load64(pr + 8), n_vblocks = load64(pr + 16);
+  r.dict_size = load64(pr + 24);
+  r.ukey_len = load32(pr + 72);
+  if (load32(pr + 76) != ct) return bad("props checksum_type differs from footer");
+  if (r.dict_size != dict_size || dict_size > 49152)
+    return bad("dict_size out of range");
+  if (r.ukey_len > 48) return bad("user key > 48 B");
+  if (r.n >= 0xffffffffull) return bad("too many entries");
+  const uint64_t kstride = (uint64_t)r.ukey_len + 28;
+  // n_kblocks/n_vblocks are bounded by the section sizes before multiplying
+  if (n_kblocks > kindex_size / kstride || n_kblocks * kstride != kindex_size)
+    return bad("key index size does not match n_kblocks");
+  if (n_vblocks > vindex_size / 24 || n_vblocks * 24 != vindex_size)
+    return bad("value index size does not match n_vblocks");
+  if ((r.n == 0) != (n_kblocks == 0) || (r.n == 0) != (n_vblocks == 0))
+    return bad("block counts do not match n");
+  r.kblocks.resize(n_kblocks);
+  for (uint64_t i = 0; i < n_kblocks; i++) {
+    const uint8_t* e = data + kindex_off + i * kstride + r.ukey_len + 8;
+    DztKeyIndexEntry& k = r.kblocks[i];
+    k.koff = load64(e);
+    k.ksize = load32(e + 8);
+    k.first_rank = load64(e + 12);
+    if (k.koff > key_size || k.ksize > key_size - k.koff)
+      return bad("key block outside the key area");
+    if (i == 0 ? k.first_rank != 0 : k.first_rank <= r.kblocks[i - 1].first_rank)
+      return bad("key index first_rank not monotone");
+    if (k.first_rank >= r.n) return bad("key index first_rank beyond n");
+    if (i && k.first_rank - r.kblocks[i - 1].first_rank > 64)
+      return bad("more than 64 records in a key block");
+  }
+  if (n_kblocks && r.n - r.kblocks.back().first_rank > 64)
+    return bad("more than 64 records in a key block");
+  r.vblocks.resize(n_vblocks);
+  for (uint64_t i = 0; i < n_vblocks; i++) {
+    const uint8_t* e = data + vindex_off + i * 24;
+    DztValueIndexEntry& v = r.vblocks[i];
+    v.voff = load64(e);
+    v.csize = load32(e + 8);
+    v.ulen = load32(e + 12);
+    v.first_rank = load64(e + 16);
+    // body + btype u8 + csum u32 inside the value area
+    if (value_size < 5 || v.voff > value_size - 5 ||
+        v.csize > value_size - 5 - v.voff)
+      return bad("value block outside the value area");
+    if (i == 0 ? v.first_rank != 0 : v.first_rank <= r.vblocks[i - 1].first_rank)
+      return bad("value index first_rank not monotone");
+    if (v.first_rank >= r.n) return bad("value index first_rank beyond n");
+  }
+  for (uint64_t i = 0; i < n_vblocks; i++) {
+    uint64_t next = i + 1 < n_vblocks ? r.vblocks[i + 1].first_rank : r.n;
+    if (r.vblocks[i].ulen > 16384 && next - r.vblocks[i].first_rank != 1)
+      return bad("value block over 16384 B holds more than one value");
+  }
+  r.dict_off = dict_off;
+  r.value_off = value_off;
+  r.kindex_off = kindex_off;
+  r.vindex_off = vindex_off;
+  r.ok = true;
+  return r;
+}
+
 ParsedSst parse_sst(const uint8_t* data, size_t size) {
   ParsedSst r;
   if (size < 53) {

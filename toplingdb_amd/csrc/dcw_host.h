@@ -96,6 +96,36 @@ struct ParsedSst {
 // footer/index/meta regions; data block BYTES go to the GPU untouched).
 ParsedSst parse_sst(const uint8_t* data, size_t size);
 
+// ---- DcwZipTable ("DZT1") input parsing (format: oracle/dzt.c) ----
+struct DztKeyIndexEntry {
+  uint64_t koff;  // in the key area
+  uint32_t ksize;
+  uint64_t first_rank;
+};
+struct DztValueIndexEntry {
+  uint64_t voff;  // in the value area
+  uint32_t csize, ulen;
+  uint64_t first_rank;
+};
+struct ParsedDzt {
+  uint32_t checksum_type = 4;
+  uint32_t ukey_len = 0;
+  uint64_t n = 0, dict_size = 0;
+  uint64_t dict_off = 0, value_off = 0, kindex_off = 0, vindex_off = 0;
+  std::vector<DztKeyIndexEntry> kblocks;
+  std::vector<DztValueIndexEntry> vblocks;
+  uint64_t key_csum_usec = 0; // host time spent on the key-area checksum
+  std::string error;
+  bool ok = false;
+};
+// true when the image ends in the 96-byte DZT footer ("DCWZIP01")
+bool is_dzt_file(const uint8_t* data, size_t size);
+// Parses footer, props and both indexes; verifies the dict, key-index,
+// value-index, props and key-area section checksums (value blocks carry
+// their own trailers and are verified on the GPU); bounds-checks every
+// index entry against its section.
+ParsedDzt parse_dzt(const uint8_t* data, size_t size);
+
 // ---- output meta tail ----
 struct TailStats {
   uint64_t num_entries = 0, num_deletions = 0, num_merge_operands = 0;

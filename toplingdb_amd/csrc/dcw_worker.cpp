@@ -269,6 +269,7 @@ struct LoadedInputs {
   bool host_decoded = false; // zstd inputs were rewritten (see below)
   // sub-phase wall attribution (printed under DCW_PHASE_DEBUG)
   uint64_t us_reserve = 0, us_pread = 0, us_parse = 0, us_stage = 0;
+  uint64_t us_dzt_keycsum = 0; // part of us_parse: DZT key-area checksums
 };
 
 // minimal libzstd ABI (runtime lib only in this image); the worker only
@@ -376,6 +377,37 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
         return -1;
       L->us_stage += now_usec() - tf;
       tf = now_usec();
+      if (is_dzt_file(L->blob.p + base, sz)) {
+        // DcwZipTable input: the tables go to the GPU job beside the
+        // BlockBasedTable block list, placed by blocks_before
+        ParsedDzt pz = parse_dzt(L->blob.p + base, sz);
+        L->us_parse += now_usec() - tf;
+        L->us_dzt_keycsum += pz.key_csum_usec;
+        if (!pz.ok) {
+          *err = std::string(path) + ": " + pz.error;
+          return -1;
+        }
+        if (cstype == 0xffffffff) cstype = pz.checksum_type;
+        if (cstype != pz.checksum_type) {
+          *err = "mixed input checksum types unsupported";
+          return -1;
+        }
+        DztFileRef zf;
+        zf.run = r;
+        zf.blocks_before = (uint32_t)L->gi.blocks.size();
+        zf.ukey_len = pz.ukey_len;
+        zf.dict_size = (uint32_t)pz.dict_size;
+        zf.n = pz.n;
+        zf.key_off = base;
+        zf.dict_off = base + pz.dict_off;
+        zf.value_off = base + pz.value_off;
+        zf.kindex_off = base + pz.kindex_off;
+        zf.kblocks = std::move(pz.kblocks);
+        zf.vblocks = std::move(pz.vblocks);
+        L->gi.dzt_files.push_back(std::move(zf));
+        L->in_bytes += sz;
+        continue;
+      }
       ParsedSst ps = parse_sst(L->blob.p + base, sz);
       L->us_parse += now_usec() - tf;
       if (!ps.ok) {
@@ -408,6 +440,11 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
       break;
     }
   L->us_parse += now_usec() - tphase;
+  if (any_zstd && !L->gi.dzt_files.empty()) {
+    // the rewrite below rebuilds the blob from BlockBasedTable blocks alone
+    *err = "zstd BlockBasedTable inputs cannot be combined with DZT inputs";
+    return -1;
+  }
   if (any_zstd) {
     if (job) { // already-streamed chunks are superseded by a full restage
       job->stage_cancel();
@@ -1062,8 +1099,15 @@ int32_t dcw_execute(const dcw_job_desc* d, dcw_job_result* res) {
     // pipeline, different build path
     int rc = dzt_finish(d, res, job, in_bytes, t_start);
     if (rc == 0 && getenv("DCW_PHASE_DEBUG"))
-      fprintf(stderr, "[phase] dzt total=%.1fms\n",
-              (now_usec() - t_start) / 1000.0);
+      fprintf(stderr,
+              "[phase] dzt total=%.1fms ms_decode=%.2f ms_merge=%.2f "
+              "ms_dedup=%.2f\n"
+              "[load] pread=%.1fms stage=%.1fms parse=%.1fms "
+              "(dzt_keycsum=%.1fms)\n",
+              (now_usec() - t_start) / 1000.0, job.ms_decode, job.ms_merge,
+              job.ms_dedup, L.us_pread / 1000.0,
+              L.us_stage / 1000.0, L.us_parse / 1000.0,
+              L.us_dzt_keycsum / 1000.0);
     return rc;
   }
 
@@ -1562,9 +1606,10 @@ int32_t dcw_execute(const dcw_job_desc* d, dcw_job_result* res) {
     fprintf(stderr, " total=%.1fms\n", (now_usec() - t_start) / 1000.0);
     fprintf(stderr,
             "[load] reset=%.1fms reserve=%.1fms pread=%.1fms stage=%.1fms "
-            "parse=%.1fms\n",
+            "parse=%.1fms (dzt_keycsum=%.1fms)\n",
             us_reset / 1000.0, L.us_reserve / 1000.0, L.us_pread / 1000.0,
-            L.us_stage / 1000.0, L.us_parse / 1000.0);
+            L.us_stage / 1000.0, L.us_parse / 1000.0,
+            L.us_dzt_keycsum / 1000.0);
   }
 
   res->num_files = (uint32_t)out_files.size();
