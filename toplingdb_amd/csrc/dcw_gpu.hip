@@ -372,7 +372,8 @@ struct GpuJob::Impl {
   DevBuf<uint64_t> d_snaps;
   // levels-below device copies
   DevBuf<uint64_t> d_lb_sm0, d_lb_sm1, d_lb_lg0, d_lb_lg1;
-  DevBuf<uint32_t> d_lb_beg;
+  DevBuf<uint32_t> d_lb_beg, d_lb_smlen, d_lb_lglen;
+  DevBuf<uint8_t> d_lb_smext, d_lb_lgext; // general-key mode: boundary bytes
   // survivors
   DevBuf<uint64_t> d_sk0, d_sk1, d_stag, d_svoff;
   DevBuf<uint32_t> d_svlen;
@@ -397,7 +398,7 @@ struct GpuJob::Impl {
   DevBuf<uint64_t> d_merge_diag;
   DevBuf<uint64_t> d_gp_sm0, d_gp_sm1, d_gp_lg0, d_gp_lg1;
   DevBuf<uint8_t> d_gp_tie, d_gp_nback;
-  DevBuf<uint32_t> d_gp_pos;
+  DevBuf<uint32_t> d_gp_pos, d_gp_smlen, d_gp_lglen;
   DevBuf<uint32_t> d_plan_next, d_plan_meta;
   DevBuf<uint16_t> d_plan_nr;
   // DZT output path
@@ -1153,21 +1154,33 @@ int GpuJob::dedup(const dcw_job_desc* d, std::string* err) {
     HIPCHK(p->h2d_meta(p->d_snaps, d->snapshots, sizeof(uint64_t) * d->num_snapshots));
     P.snapshots = p->d_snaps;
   }
-  // levels below -> normkeys
+  // levels below -> normkeys (the 16-byte prefix) + true lengths; in
+  // general-key mode also the boundary bytes a <= 48 B job key can reach
   std::vector<uint64_t> sm0, sm1, lg0, lg1;
+  std::vector<uint32_t> smlen, lglen;
+  std::vector<uint8_t> smext, lgext;
   std::vector<uint32_t> lbeg{0};
+  auto add_bound = [&](const uint8_t* k, uint32_t len, std::vector<uint64_t>& w0,
+                       std::vector<uint64_t>& w1, std::vector<uint32_t>& lens,
+                       std::vector<uint8_t>& ext) {
+    uint64_t a, b, c;
+    make_normkey(k, len, 0, &a, &b, &c);
+    w0.push_back(a);
+    w1.push_back(b);
+    lens.push_back(len);
+    if (general_keys) {
+      size_t at = ext.size();
+      ext.resize(at + DCW_GKEY_STRIDE, 0);
+      memcpy(ext.data() + at, k, len < DCW_GKEY_MAX ? len : DCW_GKEY_MAX);
+    }
+  };
   for (uint32_t l = 0; l < d->num_levels_below; l++) {
     const dcw_level_files* lf = &d->levels_below[l];
     for (uint32_t f = 0; f < lf->num_files; f++) {
-      uint64_t a, b, c;
-      make_normkey(lf->files[f].smallest_ukey, lf->files[f].smallest_len, 0, &a,
-                   &b, &c);
-      sm0.push_back(a);
-      sm1.push_back(b);
-      make_normkey(lf->files[f].largest_ukey, lf->files[f].largest_len, 0, &a, &b,
-                   &c);
-      lg0.push_back(a);
-      lg1.push_back(b);
+      add_bound(lf->files[f].smallest_ukey, lf->files[f].smallest_len, sm0, sm1,
+                smlen, smext);
+      add_bound(lf->files[f].largest_ukey, lf->files[f].largest_len, lg0, lg1,
+                lglen, lgext);
     }
     lbeg.push_back((uint32_t)sm0.size());
   }
@@ -1178,10 +1191,28 @@ int GpuJob::dedup(const dcw_job_desc* d, std::string* err) {
     HIPCHK(p->d_lb_sm1.reserve(nb));
     HIPCHK(p->d_lb_lg0.reserve(nb));
     HIPCHK(p->d_lb_lg1.reserve(nb));
+    HIPCHK(p->d_lb_smlen.reserve(nb / 2));
+    HIPCHK(p->d_lb_lglen.reserve(nb / 2));
     HIPCHK(p->h2d_meta(p->d_lb_sm0, sm0.data(), nb));
     HIPCHK(p->h2d_meta(p->d_lb_sm1, sm1.data(), nb));
     HIPCHK(p->h2d_meta(p->d_lb_lg0, lg0.data(), nb));
     HIPCHK(p->h2d_meta(p->d_lb_lg1, lg1.data(), nb));
+    HIPCHK(p->h2d_meta(p->d_lb_smlen, smlen.data(), nb / 2));
+    HIPCHK(p->h2d_meta(p->d_lb_lglen, lglen.data(), nb / 2));
+    P.lb_sm_len = p->d_lb_smlen;
+    P.lb_lg_len = p->d_lb_lglen;
+    if (general_keys) {
+      HIPCHK(p->d_lb_smext.reserve(smext.size()));
+      HIPCHK(p->d_lb_lgext.reserve(lgext.size()));
+      HIPCHK(p->h2d_meta(p->d_lb_smext, smext.data(), smext.size()));
+      HIPCHK(p->h2d_meta(p->d_lb_lgext, lgext.data(), lgext.size()));
+      P.lb_sm_ext = p->d_lb_smext;
+      P.lb_lg_ext = p->d_lb_lgext;
+    }
+  }
+  if (general_keys) {
+    P.kext = p->d_kext;
+    P.klen = p->d_klen;
   }
   HIPCHK(p->d_lb_beg.reserve(sizeof(uint32_t) * lbeg.size()));
   HIPCHK(p->h2d_meta(p->d_lb_beg, lbeg.data(), sizeof(uint32_t) * lbeg.size()));
@@ -1566,23 +1597,39 @@ int GpuJob::gp_positions(const dcw_job_desc* d, std::vector<uint32_t>* pos,
   nback->resize(n);
   if (ng == 0 || n == 0) return 0;
   std::vector<uint64_t> sm0(ng), sm1(ng), lg0(ng), lg1(ng);
+  std::vector<uint32_t> smlen(ng), lglen(ng);
   std::vector<uint8_t> tie(ng, 0);
+  if (general_keys) { // the worker refuses this before it gets here
+    if (err) *err = "grandparent cutting with general-shape keys";
+    return -1;
+  }
+  // a grandparent level may hold keys of any length: the 16-byte padded
+  // words plus the true length give raw bytewise order against the job's
+  // uniform <= 16 B keys (bound_cmp)
   for (uint32_t g = 0; g < ng; g++) {
     const dcw_grandparent& f = d->grandparents[g];
-    if (f.smallest_len != ukey_len || f.largest_len != ukey_len) {
-      if (err) *err = "grandparent user-key length differs from job keys";
-      return -1;
-    }
     uint64_t c;
     make_normkey(f.smallest_ukey, f.smallest_len, 0, &sm0[g], &sm1[g], &c);
     make_normkey(f.largest_ukey, f.largest_len, 0, &lg0[g], &lg1[g], &c);
+    smlen[g] = f.smallest_len;
+    lglen[g] = f.largest_len;
   }
-  for (uint32_t g = 0; g + 1 < ng; g++)
-    tie[g] = (lg0[g] == sm0[g + 1] && lg1[g] == sm1[g + 1]) ? 1 : 0;
+  // smallest_{g+1} == largest_g on the raw bytes (compaction_outputs.cc:
+  // 157-166), not on the padded words
+  for (uint32_t g = 0; g + 1 < ng; g++) {
+    const dcw_grandparent& f = d->grandparents[g];
+    const dcw_grandparent& nx = d->grandparents[g + 1];
+    tie[g] = (f.largest_len == nx.smallest_len &&
+              memcmp(f.largest_ukey, nx.smallest_ukey, f.largest_len) == 0)
+                 ? 1
+                 : 0;
+  }
   HIPCHK(p->d_gp_sm0.reserve(ng * 8));
   HIPCHK(p->d_gp_sm1.reserve(ng * 8));
   HIPCHK(p->d_gp_lg0.reserve(ng * 8));
   HIPCHK(p->d_gp_lg1.reserve(ng * 8));
+  HIPCHK(p->d_gp_smlen.reserve(ng * 4));
+  HIPCHK(p->d_gp_lglen.reserve(ng * 4));
   HIPCHK(p->d_gp_tie.reserve(ng));
   HIPCHK(p->d_gp_pos.reserve(n * 4));
   HIPCHK(p->d_gp_nback.reserve(n));
@@ -1590,11 +1637,13 @@ int GpuJob::gp_positions(const dcw_job_desc* d, std::vector<uint32_t>* pos,
   HIPCHK(p->h2d_meta(p->d_gp_sm1, sm1.data(), ng * 8));
   HIPCHK(p->h2d_meta(p->d_gp_lg0, lg0.data(), ng * 8));
   HIPCHK(p->h2d_meta(p->d_gp_lg1, lg1.data(), ng * 8));
+  HIPCHK(p->h2d_meta(p->d_gp_smlen, smlen.data(), ng * 4));
+  HIPCHK(p->h2d_meta(p->d_gp_lglen, lglen.data(), ng * 4));
   HIPCHK(p->h2d_meta(p->d_gp_tie, tie.data(), ng));
   hipLaunchKernelGGL(k_gp_positions, dim3(grid_for(n)), dim3(256), 0, p->stream,
-                     p->d_sk0, p->d_sk1, n, p->d_gp_sm0,
-                     p->d_gp_sm1, p->d_gp_lg0,
-                     p->d_gp_lg1, p->d_gp_tie,
+                     p->d_sk0, p->d_sk1, n, ukey_len, p->d_gp_sm0,
+                     p->d_gp_sm1, p->d_gp_smlen, p->d_gp_lg0,
+                     p->d_gp_lg1, p->d_gp_lglen, p->d_gp_tie,
                      ng, p->d_gp_pos, p->d_gp_nback);
   HIPCHK(hipMemcpyAsync(pos->data(), p->d_gp_pos, n * 4, hipMemcpyDeviceToHost,
                         p->stream));

@@ -741,13 +741,19 @@ __global__ void k_plan_next(const uint8_t* __restrict__ s_shared,
 //   pos(u) = A(u)+B(u); odd pos = inside file B(u); nback(u) = #files j <
 //   B(u) with largest_j == u (GetCurrentKeyGrandparentOverlappedBytes's
 //   backward tie loop, :218-227).
+// Every compare is raw bytewise order (bound_cmp): a grandparent key may
+// be shorter or longer than the job's uniform `ulen`-byte keys, so its true
+// length (gsmlen/glglen) breaks a tie of the padded words.
 // The host file-cut FSM consumes pos/nback per survivor.
 __global__ void k_gp_positions(const uint64_t* __restrict__ s_k0,
                                const uint64_t* __restrict__ s_k1, uint64_t n,
+                               uint32_t ulen,
                                const uint64_t* __restrict__ gsm0,
                                const uint64_t* __restrict__ gsm1,
+                               const uint32_t* __restrict__ gsmlen,
                                const uint64_t* __restrict__ glg0,
                                const uint64_t* __restrict__ glg1,
+                               const uint32_t* __restrict__ glglen,
                                const uint8_t* __restrict__ tie_next,
                                uint32_t ng, uint32_t* __restrict__ pos_out,
                                uint8_t* __restrict__ nback_out) {
@@ -758,7 +764,8 @@ __global__ void k_gp_positions(const uint64_t* __restrict__ s_k0,
     uint32_t lo = 0, hi = ng;
     while (lo < hi) {
       uint32_t mid = (lo + hi) / 2;
-      bool sm_le = gsm0[mid] < k0 || (gsm0[mid] == k0 && gsm1[mid] <= k1);
+      bool sm_le = bound_cmp(gsm0[mid], gsm1[mid], gsmlen[mid], nullptr, k0, k1,
+                             ulen, nullptr) <= 0;
       if (sm_le)
         lo = mid + 1;
       else
@@ -770,7 +777,8 @@ __global__ void k_gp_positions(const uint64_t* __restrict__ s_k0,
     hi = ng;
     while (lo < hi) {
       uint32_t mid = (lo + hi) / 2;
-      bool lg_lt = glg0[mid] < k0 || (glg0[mid] == k0 && glg1[mid] < k1);
+      bool lg_lt = bound_cmp(glg0[mid], glg1[mid], glglen[mid], nullptr, k0, k1,
+                             ulen, nullptr) < 0;
       if (lg_lt)
         lo = mid + 1;
       else
@@ -778,9 +786,12 @@ __global__ void k_gp_positions(const uint64_t* __restrict__ s_k0,
     }
     uint32_t B = lo;
     uint32_t lb = lo;
-    while (B < ng && glg0[B] == k0 && glg1[B] == k1 && tie_next[B]) B++;
+    while (B < ng && glg0[B] == k0 && glg1[B] == k1 && glglen[B] == ulen &&
+           tie_next[B])
+      B++;
     uint32_t nb = 0;
-    if (B > lb && glg0[lb] == k0 && glg1[lb] == k1) nb = B - lb;
+    if (B > lb && glg0[lb] == k0 && glg1[lb] == k1 && glglen[lb] == ulen)
+      nb = B - lb;
     pos_out[i] = A + B;
     nback_out[i] = (uint8_t)(nb > 255 ? 255 : nb);
   }

@@ -161,6 +161,16 @@ struct FsmParams {
   const uint64_t* lb_lg_k1;
   const uint32_t* lb_level_beg; // num_levels+1
   uint32_t num_levels;
+  // true byte length of each boundary: a level below may hold keys of any
+  // length, and the padded words alone cannot order "K" against "K\0"
+  const uint32_t* lb_sm_len;
+  const uint32_t* lb_lg_len;
+  // general-key mode only (null otherwise): the first DCW_GKEY_MAX bytes of
+  // each boundary at DCW_GKEY_STRIDE, and the job's full-key side table
+  const uint8_t* lb_sm_ext;
+  const uint8_t* lb_lg_ext;
+  const uint8_t* kext;
+  const uint8_t* klen;
   // range-deletion fragments (GpuJob::RdFrag SoA; envelope subset)
   const uint64_t* rd_k0;
   const uint64_t* rd_k1;
@@ -205,26 +215,61 @@ __device__ uint64_t fsm_find_earliest(const FsmParams& P, uint64_t seq,
   return lo < P.num_snapshots ? P.snapshots[lo] : kMaxSeq;
 }
 
+// Raw bytewise order (Compare(bound, key) of the bytewise comparator) of a
+// boundary user key of ANY length against a job key: <0, 0, >0.
+// (b0,b1) / (k0,k1) are the zero-padded 16-byte prefix words.  Where they
+// differ the first differing byte decides, as in raw order (a pad byte only
+// meets a real byte when the shorter key is a prefix of the longer, and 0 is
+// the smallest byte).  Where they tie, fast mode (kfull null, ulen <= 16)
+// breaks the tie on length exactly as fsm_rd_covers does; general mode
+// compares the stored bytes first.  bext holds min(blen, DCW_GKEY_MAX)
+// bytes: a job key is at most DCW_GKEY_MAX long, so of a longer boundary
+// only that prefix and "it is longer" matter.
+__device__ __forceinline__ int bound_cmp(uint64_t b0, uint64_t b1, uint32_t blen,
+                                         const uint8_t* __restrict__ bext,
+                                         uint64_t k0, uint64_t k1, uint32_t ulen,
+                                         const uint8_t* __restrict__ kfull) {
+  if (b0 != k0) return b0 < k0 ? -1 : 1;
+  if (b1 != k1) return b1 < k1 ? -1 : 1;
+  if (kfull) {
+    uint32_t m = blen < DCW_GKEY_MAX ? blen : DCW_GKEY_MAX;
+    if (ulen < m) m = ulen;
+    for (uint32_t t = 0; t < m; t++)
+      if (bext[t] != kfull[t]) return bext[t] < kfull[t] ? -1 : 1;
+  }
+  if (blen != ulen) return blen < ulen ? -1 : 1;
+  return 0;
+}
+
+// w: payload index of the group's first entry (general mode: its full key)
 __device__ bool fsm_key_not_exists_beyond(const FsmParams& P, uint64_t k0,
-                                          uint64_t k1) {
+                                          uint64_t k1, uint64_t w) {
   if (P.bottommost) return true;
   if (!P.levels_below_valid) return false; // reference worker branch
+  const uint8_t* kfull = P.kext ? P.kext + w * DCW_GKEY_STRIDE : nullptr;
+  uint32_t ulen = P.kext ? (uint32_t)P.klen[w] - 8 : P.rd_ukey_len;
   for (uint32_t lvl = 0; lvl < P.num_levels; lvl++) {
     uint32_t b = P.lb_level_beg[lvl], e = P.lb_level_beg[lvl + 1];
     // first file with largest >= key
     uint32_t lo = b, hi = e;
     while (lo < hi) {
       uint32_t mid = (lo + hi) / 2;
-      bool lg_lt = P.lb_lg_k0[mid] < k0 ||
-                   (P.lb_lg_k0[mid] == k0 && P.lb_lg_k1[mid] < k1);
+      // compaction.cc:566: Compare(user_key, largest) <= 0 ends the walk
+      bool lg_lt =
+          bound_cmp(P.lb_lg_k0[mid], P.lb_lg_k1[mid], P.lb_lg_len[mid],
+                    kfull ? P.lb_lg_ext + (uint64_t)mid * DCW_GKEY_STRIDE : nullptr,
+                    k0, k1, ulen, kfull) < 0;
       if (lg_lt)
         lo = mid + 1;
       else
         hi = mid;
     }
     if (lo < e) {
-      bool sm_le = P.lb_sm_k0[lo] < k0 ||
-                   (P.lb_sm_k0[lo] == k0 && P.lb_sm_k1[lo] <= k1);
+      // compaction.cc:573-577: Compare(user_key, smallest) >= 0 -> may exist
+      bool sm_le =
+          bound_cmp(P.lb_sm_k0[lo], P.lb_sm_k1[lo], P.lb_sm_len[lo],
+                    kfull ? P.lb_sm_ext + (uint64_t)lo * DCW_GKEY_STRIDE : nullptr,
+                    k0, k1, ulen, kfull) <= 0;
       if (sm_le) return false;
     }
   }
@@ -309,7 +354,8 @@ __global__ void k_group_fsm(const ulong4* __restrict__ e, uint64_t n,
             out_this = true; // kKeepSDForSnapshot
           }
         } else {
-          if (seq <= P.earliest_snapshot && fsm_key_not_exists_beyond(P, k0, k1)) {
+          if (seq <= P.earliest_snapshot &&
+              fsm_key_not_exists_beyond(P, k0, k1, e[g0].w)) {
             // drop (fallthrough SD)
           } else if (last_zeroed) {
             // drop
@@ -321,7 +367,7 @@ __global__ void k_group_fsm(const ulong4* __restrict__ e, uint64_t n,
                  (last_snapshot > 0 && last_snapshot < cukSnap)) {
         // rule (A): hidden by newer entry in the same snapshot stripe
       } else if (type == kTypeDeletion && seq <= P.earliest_snapshot &&
-                 fsm_key_not_exists_beyond(P, k0, k1)) {
+                 fsm_key_not_exists_beyond(P, k0, k1, e[g0].w)) {
         // obsolete delete
       } else if (type == kTypeDeletion && P.bottommost) {
         // skip versions in the same snapshot range
