@@ -1,9 +1,13 @@
 // dcw_host.cpp — implementation of dcw_host.h (see header for citations).
 #include "dcw_host.h"
 
+#include <fcntl.h>
+#include <unistd.h>
+
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <future>
 
 namespace dcw {
 
@@ -632,6 +636,234 @@ std::vector<PlannedBlock> plan_blocks(const PlanIn& in, size_t from,
     produced += b.unc_size + kTrailerSize;
   }
   return out;
+}
+
+// ---------------- file cutting ----------------
+FileCutter::FileCutter(uint64_t target_file_size, uint64_t max_compaction_bytes,
+                       bool level_compaction_dynamic_file_size,
+                       uint32_t num_grandparents, const uint32_t* gp_pos,
+                       const uint8_t* gp_nback, const uint64_t* gp_file_sizes)
+    : target_(target_file_size),
+      max_compaction_bytes_(max_compaction_bytes),
+      dyn_(level_compaction_dynamic_file_size),
+      ngp_(num_grandparents),
+      gp_pos_(num_grandparents ? gp_pos : nullptr),
+      gp_nback_(gp_nback),
+      gp_psum_(num_grandparents + 1, 0) {
+  for (uint32_t g = 0; g < ngp_; g++)
+    gp_psum_[g + 1] = gp_psum_[g] + gp_file_sizes[g];
+}
+
+uint64_t FileCutter::gp_cur_overlap(uint64_t e) const {
+  uint32_t p = gp_pos_[e];
+  if ((p & 1) == 0) return 0; // in gap
+  uint32_t idx = (p - 1) / 2;
+  uint32_t nb = gp_nback_[e];
+  return gp_psum_[idx + 1] - gp_psum_[idx - nb];
+}
+
+uint64_t FileCutter::gp_update(uint64_t e) {
+  uint32_t newpos = gp_pos_[e];
+  uint64_t crossings = 0;
+  if (seen_key_) {
+    crossings = newpos - last_pos_;
+    if (newpos >= 1 && crossings > 0) {
+      uint64_t f_lo = (last_pos_ + 1) / 2; // files entered in span
+      uint64_t f_hi = (newpos - 1) / 2;
+      if (f_hi >= f_lo && f_lo < ngp_) {
+        if (f_hi >= ngp_) f_hi = ngp_ - 1;
+        overlapped_ += gp_psum_[f_hi + 1] - gp_psum_[f_lo];
+      }
+    }
+    switched_ += crossings;
+  } else if (newpos & 1) {
+    overlapped_ = gp_cur_overlap(e); // first key lands mid-file
+  }
+  seen_key_ = true;
+  last_pos_ = newpos;
+  return crossings;
+}
+
+CutRule FileCutter::should_stop(uint64_t e, uint64_t off, uint64_t crossings,
+                                uint64_t prev_overlapped) const {
+  if (off >= target_) return CutRule::kSize;
+  if (crossings == 0) return CutRule::kNone;
+  if (overlapped_ + off > max_compaction_bytes_)
+    return CutRule::kMaxCompactionBytes;
+  if (!dyn_) return CutRule::kNone;
+  bool in_gap = (gp_pos_[e] & 1) == 0;
+  uint64_t skippable = in_gap ? 2 : 3;
+  if (crossings >= skippable && overlapped_ - prev_overlapped > target_ / 8)
+    return CutRule::kDynamic;
+  uint64_t sw5 = switched_ * 5 < 40 ? switched_ * 5 : 40;
+  if (off >= ((target_ + 99) / 100) * (50 + sw5)) return CutRule::kDynamic;
+  return CutRule::kNone;
+}
+
+FileCut FileCutter::next_chunk(const std::vector<PlannedBlock>& blocks,
+                               const std::vector<uint32_t>& csizes,
+                               uint64_t data_size, size_t s, size_t nsurv) {
+  FileCut c;
+  c.take = blocks.size();
+  uint64_t off = data_size;
+  if (!gp_pos_) {
+    for (size_t b = 0; b < blocks.size(); b++) {
+      off += csizes[b] + kTrailerSize;
+      bool more_entries = blocks[b].first + blocks[b].count < nsurv;
+      if (off >= target_ && more_entries) {
+        c.cut = true;
+        c.rule = CutRule::kSize;
+        c.take = b + 1;
+        c.partial_first = blocks[b].first + blocks[b].count; // e0
+        c.partial_count = 1;
+        c.cut_entry = c.partial_first + 1; // next file starts after e0
+        break;
+      }
+    }
+    return c;
+  }
+  for (size_t b = 0; b < blocks.size(); b++) {
+    for (uint32_t li = 0; li < blocks[b].count; li++) {
+      uint64_t e = blocks[b].first + li;
+      // (1) ShouldStopBefore(e): grandparent update, then cut rules
+      uint64_t prev_overlapped = overlapped_;
+      uint64_t crossings = gp_update(e);
+      bool has_builder = e != s; // builder empty before the file's first Add
+      if (has_builder && e < nsurv) {
+        CutRule rule = should_stop(e, off, crossings, prev_overlapped);
+        if (rule != CutRule::kNone) {
+          c.cut = true;
+          c.rule = rule;
+          c.cut_entry = e; // next file starts AT e
+          c.take = b;      // full blocks before the current one
+          c.partial_first = blocks[b].first;
+          c.partial_count = li; // may be 0 (cut at a block boundary)
+          // close-file resets (compaction_outputs.cc:374-380)
+          switched_ = 0;
+          overlapped_ = gp_cur_overlap(e);
+          return c;
+        }
+      }
+      // (2) Add(e): the flush of the previous block happens here
+      if (li == 0 && b > 0) off += csizes[b - 1] + kTrailerSize;
+    }
+  }
+  return c;
+}
+
+// ---------------- range-tombstone fragments ----------------
+std::vector<TombstoneFragment> fragment_tombstones(
+    const std::vector<SstTombstone>& tombstones) {
+  std::vector<std::string> bounds;
+  for (auto& t : tombstones) {
+    bounds.push_back(t.start);
+    bounds.push_back(t.end);
+  }
+  std::sort(bounds.begin(), bounds.end());
+  bounds.erase(std::unique(bounds.begin(), bounds.end()), bounds.end());
+  std::vector<TombstoneFragment> frags;
+  for (size_t i = 0; i < bounds.size(); i++) {
+    uint64_t mx = 0;
+    if (i + 1 < bounds.size())
+      for (auto& t : tombstones)
+        if (t.start <= bounds[i] && bounds[i] < t.end && t.seq > mx) mx = t.seq;
+    TombstoneFragment fr;
+    uint64_t c;
+    make_normkey((const uint8_t*)bounds[i].data(), (uint32_t)bounds[i].size(),
+                 0, &fr.k0, &fr.k1, &c);
+    fr.len = (uint32_t)bounds[i].size();
+    fr.max_seq = mx;
+    frags.push_back(fr);
+  }
+  return frags;
+}
+
+// ---------------- DcwZipTable output plan ----------------
+std::vector<DztFilePlan> dzt_plan_files(const uint32_t* vlen,
+                                        const uint8_t* shared, size_t nsurv,
+                                        uint32_t U, uint64_t target_file_size) {
+  std::vector<DztFilePlan> files;
+  uint64_t i = 0;
+  while (i < nsurv) {
+    DztFilePlan fp; // out_open
+    fp.first = i;
+    uint64_t unc = 0, vb_stage = 0, vb_first = i, vb_ulen = 0;
+    uint32_t vb_count = 0;
+    auto close_value_block = [&]() {
+      fp.vbs.push_back({(uint32_t)vb_first, vb_count, (uint32_t)vb_ulen,
+                        vb_stage});
+      vb_stage += vb_ulen;
+    };
+    while (i < nsurv) { // out_add(entry i)
+      uint32_t vl = vlen[i];
+      bool vb_closes = vb_count >= kDztVbMax ||
+                       (vb_count > 0 && vb_ulen + vl > kDztVbUlenMax);
+      if (vb_closes && fp.count > 0 && unc >= target_file_size)
+        break; // out_close: file cut before entry i
+      if (vb_closes) {
+        close_value_block();
+        vb_first = i;
+        vb_count = 0;
+        vb_ulen = 0;
+      }
+      uint64_t fl = i - fp.first;
+      bool opens_key_block = fl % kDztKB == 0;
+      if (opens_key_block) fp.kbs.push_back({(uint32_t)i, 0, fp.key_area_size});
+      uint32_t sh = opens_key_block ? 0 : (shared[i] < U ? shared[i] : U);
+      uint32_t ns = U - sh;
+      uint32_t krec = varint_len(sh) + varint_len(ns) + ns + 8 + 4 + 4;
+      fp.kbs.back().count++;
+      fp.key_area_size += krec;
+      fp.voff.push_back((uint32_t)vb_ulen);
+      vb_count++;
+      vb_ulen += vl;
+      unc += krec + vl;
+      fp.raw_value += vl;
+      fp.count++;
+      i++;
+    }
+    if (vb_count) close_value_block();
+    if (fp.count) files.push_back(std::move(fp));
+  }
+  return files;
+}
+
+// ---------------- segmented file write ----------------
+namespace {
+bool pwrite_all(int fd, const uint8_t* src, size_t cnt, size_t off) {
+  size_t done = 0;
+  while (done < cnt) {
+    ssize_t w = pwrite(fd, src + done, cnt - done, (off_t)(off + done));
+    if (w <= 0) return false;
+    done += (size_t)w;
+  }
+  return true;
+}
+} // namespace
+
+bool write_file_segmented(const char* path, const uint8_t* data, size_t len,
+                          size_t seg_bytes, size_t max_segs) {
+  int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (fd < 0) return false;
+  if (ftruncate(fd, (off_t)len) != 0) {
+    close(fd);
+    return false;
+  }
+  size_t nseg = (len + seg_bytes - 1) / seg_bytes;
+  if (nseg > max_segs) nseg = max_segs;
+  if (nseg == 0) nseg = 1;
+  size_t seg = (len + nseg - 1) / nseg;
+  std::vector<std::future<bool>> segw;
+  for (size_t si = 1; si < nseg; si++) {
+    size_t off = si * seg;
+    size_t cnt = off < len ? std::min(seg, len - off) : 0;
+    segw.emplace_back(std::async(std::launch::async, pwrite_all, fd,
+                                 data + off, cnt, off));
+  }
+  bool ok = pwrite_all(fd, data, std::min(seg, len), 0);
+  for (auto& f : segw) ok = f.get() && ok;
+  close(fd);
+  return ok;
 }
 
 // ---------------- TableWriter (sstgen + partial blocks) ----------------

@@ -155,7 +155,6 @@ struct PlanIn { // per-survivor metadata (D2H from the GPU)
   const uint8_t* shared;  // prefix shared with previous survivor (full ikey)
   const uint8_t* klen;    // internal key length
   const uint32_t* vlen;   // value length
-  const uint32_t* gp_pos; // grandparent boundary position index (may be null)
   size_t n;
 };
 struct PlannedBlock {
@@ -171,18 +170,121 @@ std::vector<PlannedBlock> plan_blocks(const PlanIn& in, size_t from,
                                       const TableOpts& o, uint64_t min_bytes,
                                       std::vector<uint32_t>* eoff_out = nullptr);
 
-// grandparent accounting state (compaction_outputs.cc:121-230), driven by
-// per-entry boundary positions precomputed on the GPU:
+// ---- file cutting (ShouldStopBefore, compaction_outputs.cc:231-352) ----
+// Decides where an output file ends, one call per emitted chunk of blocks.
+// Without grandparents the file size only changes at block flushes, so the
+// walk is block-level and the cut lands one entry after the crossing flush
+// (the open block then holds exactly one entry).  With grandparents every
+// entry is checked against the boundary-crossing rules and the cut may land
+// mid-block.  The grandparent accounting (compaction_outputs.cc:121-230) is
+// driven by per-survivor boundary positions precomputed on the GPU:
 // gp_pos[i] = number of grandparent boundary points (smallest_0, largest_0,
-// smallest_1, ...) that are "passed" by survivor i's user key under the
-// reference's walk (see kernel gp_positions).  being_in_gap = pos is even.
-struct FileCutState {
-  uint64_t current_output_file_size = 0;
-  uint64_t gp_overlapped_bytes = 0;
-  size_t gp_boundary_switched_num = 0;
-  uint32_t last_gp_pos = 0;
-  bool seen_key = false;
+// smallest_1, ...) "passed" by survivor i's user key under the reference's
+// walk, gp_nback[i] = files before the current one whose largest equals the
+// key (see k_gp_positions).  being_in_gap = pos is even.
+enum class CutRule : uint8_t { kNone, kSize, kMaxCompactionBytes, kDynamic };
+struct FileCut {
+  bool cut = false;
+  size_t take = 0;            // full blocks of the chunk that the file keeps
+  uint64_t partial_first = 0; // mid-block remainder [partial_first, cut_entry)
+  uint32_t partial_count = 0; // may be 0 (cut at a block boundary)
+  uint64_t cut_entry = 0;     // first entry of the next file
+  CutRule rule = CutRule::kNone; // which rule cut (reported by tools only)
 };
+class FileCutter {
+ public:
+  // One per job.  gp_pos / gp_nback are null when num_grandparents == 0 and
+  // must outlive the cutter; gp_file_sizes has num_grandparents elements.
+  FileCutter(uint64_t target_file_size, uint64_t max_compaction_bytes,
+             bool level_compaction_dynamic_file_size,
+             uint32_t num_grandparents, const uint32_t* gp_pos,
+             const uint8_t* gp_nback, const uint64_t* gp_file_sizes);
+  // blocks/csizes: the chunk just emitted, in order, continuing a file whose
+  // data blocks so far take `data_size` bytes and whose first survivor is
+  // `s`; nsurv = survivors of the job.
+  FileCut next_chunk(const std::vector<PlannedBlock>& blocks,
+                     const std::vector<uint32_t>& csizes, uint64_t data_size,
+                     size_t s, size_t nsurv);
+
+ private:
+  // GetCurrentKeyGrandparentOverlappedBytes (compaction_outputs.cc:189-229)
+  uint64_t gp_cur_overlap(uint64_t e) const;
+  // UpdateGrandparentBoundaryInfo for entry e: returns the boundaries crossed
+  uint64_t gp_update(uint64_t e);
+  CutRule should_stop(uint64_t e, uint64_t off, uint64_t crossings,
+                      uint64_t prev_overlapped) const;
+
+  uint64_t target_, max_compaction_bytes_;
+  bool dyn_;
+  uint32_t ngp_;
+  const uint32_t* gp_pos_;
+  const uint8_t* gp_nback_;
+  std::vector<uint64_t> gp_psum_; // prefix sums of the grandparent file sizes
+  // Walk state.  It runs across the files of one job: only a cut resets
+  // part of it (close-file resets, compaction_outputs.cc:374-380).
+  bool seen_key_ = false;
+  uint64_t last_pos_ = 0;
+  uint64_t overlapped_ = 0; // grandparent_overlapped_bytes_
+  uint64_t switched_ = 0;   // grandparent_boundary_switched_num_
+};
+
+// ---- range-tombstone fragments ----
+// Fragment i covers user keys in [start_i, start_{i+1}); max_seq 0 marks a
+// gap or the terminator.  Same construction as the oracle's rd_aggr,
+// including the zero-seq gap/terminator fragments; sorted by start key.
+// Bounds must be <= 16 B (the caller checks the envelope).
+struct TombstoneFragment {
+  uint64_t k0, k1; // zero-padded big-endian start-key words
+  uint32_t len;    // true byte length (zero-pad tie-break)
+  uint64_t max_seq;
+};
+std::vector<TombstoneFragment> fragment_tombstones(
+    const std::vector<SstTombstone>& tombstones);
+
+// ---- DcwZipTable ("DZT1") output plan ----
+// Mirrors the oracle's DZT out_add/out_close rule (oracle/compact.c DZT
+// branch; format: oracle/dzt.c): value blocks group greedily (<= 256 values,
+// <= 16 KiB), a file is cut where an entry would open a new value block and
+// the file's uncompressed bytes reached the target, key blocks hold 64.
+enum : uint32_t {
+  kDztKB = 64,
+  kDztVbMax = 256,
+  kDztVbUlenMax = 16384,
+  kDztDictMax = 49152,
+  kDztDictSampleBytes = 256,
+};
+struct DztValueBlockPlan {
+  uint32_t first;     // survivor index of the block's first entry (absolute)
+  uint32_t count;
+  uint32_t ulen;      // uncompressed value bytes
+  uint64_t stage_off; // offset in the file's value staging area
+};
+struct DztKeyBlockPlan {
+  uint32_t first; // absolute survivor index
+  uint32_t count; // <= kDztKB
+  uint64_t koff;  // offset in the key area
+};
+struct DztFilePlan {
+  uint64_t first = 0, count = 0; // survivor range
+  std::vector<DztValueBlockPlan> vbs;
+  std::vector<DztKeyBlockPlan> kbs;
+  std::vector<uint32_t> voff; // per entry (file-local order): offset in its value block
+  uint64_t key_area_size = 0;
+  uint64_t raw_value = 0;
+};
+// vlen / shared: per-survivor value length and internal-key prefix shared
+// with the previous survivor; U = uniform user-key length.
+std::vector<DztFilePlan> dzt_plan_files(const uint32_t* vlen,
+                                        const uint8_t* shared, size_t nsurv,
+                                        uint32_t U, uint64_t target_file_size);
+
+// ---- segmented file write ----
+// Creates/truncates `path` and writes data[0, len) as up to max_segs
+// segments of about seg_bytes each, one pwrite loop per segment on its own
+// transient thread (the caller's thread writes the first).  tmpfs writes are
+// page-clear + memcpy bound per thread.  Returns false on any failure.
+bool write_file_segmented(const char* path, const uint8_t* data, size_t len,
+                          size_t seg_bytes, size_t max_segs);
 
 // ---- synthetic input generator (harness; the DB host's write path
 //      stand-in, tools/db_bench_tool.cc:3468) ----
