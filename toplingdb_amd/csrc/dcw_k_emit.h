@@ -3,6 +3,7 @@
 // dcw_k_*.h headers in order, inside one unit, so every kernel is defined
 // before the host code that launches it.  Not a stand-alone header.
 #pragma once
+#include "dcw_snap_enc_big.h"
 
 namespace dcw {
 
@@ -62,6 +63,7 @@ struct EmitBlockDesc {
   uint32_t unc_size;  // total uncompressed block size (with restarts+footer)
   uint32_t num_restarts;
   uint64_t uout;      // offset into ucblob
+  uint64_t cout;      // offset of the block's compressed-output slot in cblob
 };
 
 // one workgroup per block; thread 0 walks the block's entry sizes into an
@@ -154,7 +156,7 @@ __global__ void k_emit(const EmitBlockDesc* __restrict__ bds, uint32_t nblocks,
 // the block's output slot.  The segment encoder itself is
 // dcw::snap_encode_segment — the SAME function the host C++ restatement
 // runs, so device/host byte-parity holds by construction.
-#define SNAP_MAX_UNC 16384 // block_size + slack; host guards this bound
+#define SNAP_MAX_UNC 16384 // larger blocks go to k_compress_large (below)
 #define SNAP_MAX_OUT (32 + SNAP_MAX_UNC + SNAP_MAX_UNC / 6)
 #define SNAP_FRAG_MAX 304 // worst-case encode of one <=256 B segment
 
@@ -244,8 +246,7 @@ __device__ __forceinline__ void lds_min_u16(uint16_t* tab, uint32_t h,
 __global__ __launch_bounds__(256, 8) void k_compress(
     const EmitBlockDesc* __restrict__ bds, uint32_t nblocks,
     const uint8_t* __restrict__ ucblob, uint8_t* __restrict__ cblob,
-    uint64_t ccap_per_block, uint32_t* __restrict__ bsize,
-    uint8_t* __restrict__ btype, uint32_t* err_flag) {
+    uint32_t* __restrict__ bsize, uint8_t* __restrict__ btype) {
   // u16 positions halve the table to 4 KiB per wave: 16 KiB per
   // workgroup lifts LDS-limited occupancy 20 -> 28 waves/CU (SGPR-bound),
   // which is what a latency-chain-bound kernel wants; emitted bytes are
@@ -258,14 +259,7 @@ __global__ __launch_bounds__(256, 8) void k_compress(
   for (uint32_t b = blockIdx.x * waves + wid; b < nblocks;
        b += gridDim.x * waves) {
     EmitBlockDesc d = bds[b];
-    if (d.unc_size > SNAP_MAX_UNC) {
-      if (lane == 0) {
-        set_err(err_flag, DE_BLOCK_PARSE);
-        bsize[b] = d.unc_size;
-        btype[b] = 0;
-      }
-      continue;
-    }
+    if (d.unc_size > SNAP_MAX_UNC) continue; // k_compress_large's block
     const uint8_t* gin = ucblob + d.uout;
     uint32_t n = d.unc_size;
     {
@@ -296,7 +290,7 @@ __global__ __launch_bounds__(256, 8) void k_compress(
     }
     uint32_t total = __shfl(inc, WAVE - 1);
     uint32_t excl = inc - fl;
-    uint8_t* gout = cblob + (uint64_t)b * ccap_per_block;
+    uint8_t* gout = cblob + d.cout;
     uint8_t hdr[5];
     uint32_t hl = varint32_put(hdr, n); // lane-uniform
     if (lane == 0)
@@ -391,8 +385,7 @@ __device__ __forceinline__ uint32_t snap_measure_segment_dev(
 __global__ __launch_bounds__(256) void k_compress_ldsin(
     const EmitBlockDesc* __restrict__ bds, uint32_t nblocks,
     const uint8_t* __restrict__ ucblob, uint8_t* __restrict__ cblob,
-    uint64_t ccap_per_block, uint32_t* __restrict__ bsize,
-    uint8_t* __restrict__ btype, uint32_t* err_flag) {
+    uint32_t* __restrict__ bsize, uint8_t* __restrict__ btype) {
   __shared__ uint16_t tabs[4][1u << kSnapHashBits]; // 4 KiB per wave
   __shared__ uint8_t ins[4][5376];
   uint32_t wid = threadIdx.x / WAVE;
@@ -402,14 +395,7 @@ __global__ __launch_bounds__(256) void k_compress_ldsin(
   for (uint32_t b = blockIdx.x * waves + wid; b < nblocks;
        b += gridDim.x * waves) {
     EmitBlockDesc d = bds[b];
-    if (d.unc_size > SNAP_MAX_UNC) {
-      if (lane == 0) {
-        set_err(err_flag, DE_BLOCK_PARSE);
-        bsize[b] = d.unc_size;
-        btype[b] = 0;
-      }
-      continue;
-    }
+    if (d.unc_size > SNAP_MAX_UNC) continue; // k_compress_large's block
     const uint8_t* gin = ucblob + d.uout;
     uint32_t n = d.unc_size;
     const uint8_t* in = gin;
@@ -454,7 +440,7 @@ __global__ __launch_bounds__(256) void k_compress_ldsin(
     }
     uint32_t total = __shfl(inc, WAVE - 1);
     uint32_t excl = inc - fl;
-    uint8_t* gout = cblob + (uint64_t)b * ccap_per_block;
+    uint8_t* gout = cblob + d.cout;
     uint8_t hdr[5];
     uint32_t hl = varint32_put(hdr, n);
     if (lane == 0)
@@ -488,8 +474,7 @@ template <int LDSIN>
 __global__ __launch_bounds__(256, 8) void k_compress_2p(
     const EmitBlockDesc* __restrict__ bds, uint32_t nblocks,
     const uint8_t* __restrict__ ucblob, uint8_t* __restrict__ cblob,
-    uint64_t ccap_per_block, uint32_t* __restrict__ bsize,
-    uint8_t* __restrict__ btype, uint32_t* err_flag) {
+    uint32_t* __restrict__ bsize, uint8_t* __restrict__ btype) {
   __shared__ uint16_t tabs[4][1u << kSnapHashBits]; // 4 KiB per wave
   __shared__ uint8_t ins[LDSIN ? 4 : 1][LDSIN ? SNAP_LDSIN_MAX : 4];
   uint32_t wid = threadIdx.x / WAVE;
@@ -499,14 +484,7 @@ __global__ __launch_bounds__(256, 8) void k_compress_2p(
   for (uint32_t b = blockIdx.x * waves + wid; b < nblocks;
        b += gridDim.x * waves) {
     EmitBlockDesc d = bds[b];
-    if (d.unc_size > SNAP_MAX_UNC) {
-      if (lane == 0) {
-        set_err(err_flag, DE_BLOCK_PARSE);
-        bsize[b] = d.unc_size;
-        btype[b] = 0;
-      }
-      continue;
-    }
+    if (d.unc_size > SNAP_MAX_UNC) continue; // k_compress_large's block
     const uint8_t* gin = ucblob + d.uout;
     uint32_t n = d.unc_size;
     const uint8_t* in = gin;
@@ -552,7 +530,7 @@ __global__ __launch_bounds__(256, 8) void k_compress_2p(
     // GoodCompressionRatio check BEFORE emitting: incompressible blocks
     // write nothing (pack copies the raw block)
     if (cn <= (((uint64_t)896 * n) >> 10)) {
-      uint8_t* gout = cblob + (uint64_t)b * ccap_per_block;
+      uint8_t* gout = cblob + d.cout;
       if (lane == 0) {
         for (uint32_t t = 0; t < hl; t++) gout[t] = hdr[t];
         bsize[b] = cn;
@@ -567,9 +545,93 @@ __global__ __launch_bounds__(256, 8) void k_compress_2p(
   }
 }
 
+// ---- large blocks: unc_size > SNAP_MAX_UNC ----
+// Same structure as k_compress — one wave per block, all 64 lanes build the
+// first-occurrence table, lane i owns segment i — for blocks of any size
+// below 2^31.  `big` lists the block indices (the host knows every
+// unc_size from the plan).  What changes against the default kernel:
+//   - u32 positions (8 KiB of LDS per wave) under plain LDS atomicMin:
+//     positions pass 0xffff at n = 65539
+//   - no per-lane fragment buffer, a segment is n/64 bytes: two passes as
+//     in k_compress_2p.  Pass 1 measures, a shfl prefix sum places the
+//     fragments, the ratio test runs on the measured size, and only an
+//     accepted block runs pass 2, which writes straight to the slot.  A
+//     rejected block writes nothing and is stored raw.
+//   - the general measure/emit pair of dcw_snap_enc_big.h (long literal
+//     headers, 4-byte-offset copies)
+// Writes stay inside the slot: pass 2 runs only when hl + total <=
+// (896*n) >> 10 < n, and the slot holds snappy_max_compressed(n) > n bytes.
+// n >= 2^31 is refused (DE_BLOCK_PARSE): the 32-bit prefix sums and
+// snappy_max_compressed would wrap.
+#define SNAP_LARGE_MAX_UNC 0x7fffffffu
+__global__ __launch_bounds__(256) void k_compress_large(
+    const EmitBlockDesc* __restrict__ bds, const uint32_t* __restrict__ big,
+    uint32_t nbig, const uint8_t* __restrict__ ucblob,
+    uint8_t* __restrict__ cblob, uint32_t* __restrict__ bsize,
+    uint8_t* __restrict__ btype, uint32_t* err_flag) {
+  __shared__ uint32_t tabs[4][1u << kSnapHashBits]; // 8 KiB per wave
+  uint32_t wid = threadIdx.x / WAVE;
+  uint32_t lane = threadIdx.x % WAVE;
+  uint32_t waves = blockDim.x / WAVE;
+  uint32_t* tab = tabs[wid];
+  for (uint32_t i = blockIdx.x * waves + wid; i < nbig;
+       i += gridDim.x * waves) {
+    uint32_t b = big[i];
+    EmitBlockDesc d = bds[b];
+    uint32_t n = d.unc_size;
+    if (n > SNAP_LARGE_MAX_UNC) {
+      if (lane == 0) {
+        set_err(err_flag, DE_BLOCK_PARSE);
+        bsize[b] = n;
+        btype[b] = 0;
+      }
+      continue;
+    }
+    const uint8_t* gin = ucblob + d.uout;
+    for (uint32_t t = lane; t < (1u << kSnapHashBits); t += WAVE)
+      tab[t] = 0xffffffffu;
+    wave_lds_sync();
+    for (uint32_t p = lane; p + 4 <= n; p += WAVE) {
+      uint32_t h = (load32(gin + p) * kSnapHashMul) >> (32 - kSnapHashBits);
+      atomicMin(&tab[h], p);
+    }
+    wave_lds_sync();
+    uint32_t seg = (uint32_t)snap_segment_size(n); // <= 2^25: lane*seg fits
+    uint32_t s0 = lane * seg;
+    uint32_t s1 = s0 + seg < n ? s0 + seg : n;
+    uint32_t fl =
+        s0 < n ? snapb_walk_segment<false>(gin, s0, s1, tab, nullptr) : 0;
+    uint32_t inc = fl;
+    for (int sh = 1; sh < WAVE; sh <<= 1) {
+      uint32_t v = __shfl_up(inc, sh);
+      if ((int)lane >= sh) inc += v;
+    }
+    uint32_t total = __shfl(inc, WAVE - 1);
+    uint32_t excl = inc - fl;
+    uint8_t hdr[5];
+    uint32_t hl = varint32_put(hdr, n); // lane-uniform
+    uint64_t cn = (uint64_t)hl + total;
+    // GoodCompressionRatio before any store, as in k_compress_2p
+    if (cn <= (((uint64_t)896 * n) >> 10)) {
+      uint8_t* gout = cblob + d.cout;
+      if (lane == 0) {
+        for (uint32_t t = 0; t < hl; t++) gout[t] = hdr[t];
+        bsize[b] = (uint32_t)cn;
+        btype[b] = 1;
+      }
+      if (s0 < n)
+        (void)snapb_walk_segment<true>(gin, s0, s1, tab, gout + hl + excl);
+    } else if (lane == 0) {
+      bsize[b] = n;
+      btype[b] = 0;
+    }
+    wave_lds_sync();
+  }
+}
+
 __global__ void k_checksum(const EmitBlockDesc* __restrict__ bds, uint32_t nblocks,
                            const uint8_t* __restrict__ ucblob,
-                           const uint8_t* __restrict__ cblob, uint64_t ccap,
+                           const uint8_t* __restrict__ cblob,
                            const uint32_t* __restrict__ bsize,
                            const uint8_t* __restrict__ btype,
                            uint32_t checksum_type,
@@ -578,7 +640,7 @@ __global__ void k_checksum(const EmitBlockDesc* __restrict__ bds, uint32_t nbloc
   for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < nblocks;
        b += gridDim.x * blockDim.x) {
     const uint8_t* body =
-        btype[b] ? cblob + (uint64_t)b * ccap : ucblob + bds[b].uout;
+        btype[b] ? cblob + bds[b].cout : ucblob + bds[b].uout;
     csum[b] = block_checksum(checksum_type, crc_tt, body, bsize[b], btype[b]);
   }
 }
@@ -586,7 +648,7 @@ __global__ void k_checksum(const EmitBlockDesc* __restrict__ bds, uint32_t nbloc
 // pack [body|trailer]* into a contiguous image at host-provided offsets
 __global__ void k_pack(const EmitBlockDesc* __restrict__ bds, uint32_t b0,
                        uint32_t b1, const uint8_t* __restrict__ ucblob,
-                       const uint8_t* __restrict__ cblob, uint64_t ccap,
+                       const uint8_t* __restrict__ cblob,
                        const uint32_t* __restrict__ bsize,
                        const uint8_t* __restrict__ btype,
                        const uint32_t* __restrict__ csum,
@@ -596,7 +658,7 @@ __global__ void k_pack(const EmitBlockDesc* __restrict__ bds, uint32_t b0,
   uint32_t wave = blockIdx.x * waves_per_wg + threadIdx.x / WAVE;
   uint32_t lane = threadIdx.x % WAVE;
   for (uint32_t b = b0 + wave; b < b1; b += gridDim.x * waves_per_wg) {
-    const uint8_t* body = btype[b] ? cblob + (uint64_t)b * ccap : ucblob + bds[b].uout;
+    const uint8_t* body = btype[b] ? cblob + bds[b].cout : ucblob + bds[b].uout;
     uint8_t* dst = out + outoff[b - b0];
     uint32_t n = bsize[b];
     for (uint32_t posn = lane * 16; posn < n; posn += WAVE * 16) {
