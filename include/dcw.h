@@ -66,7 +66,10 @@ enum {
  * DcwZipTable ("DZT1", the worker's own output_table_factory = 1 format);
  * the kind is detected per file from its footer magic, and the two kinds
  * may be mixed freely, across runs and inside one run.  All inputs of a job
- * must share one checksum_type. */
+ * must share one checksum_type.  User keys may have any mix of lengths up to
+ * 48 bytes.  Range tombstones in the inputs (bounds of any length) are
+ * applied when the job is bottommost with no snapshots and no grandparents;
+ * outside that the job fails with status 29. */
 typedef struct dcw_run {
   const char* const* files; /* SST paths, in key order for level runs */
   uint32_t num_files;
@@ -155,7 +158,10 @@ typedef struct dcw_job_desc {
    * 1 = DcwZipTable "DZT1": the searchable-compressed SST of BASELINE.json
    *     configs[3] (the reference's ToplingZipTable is absent/private,
    *     README.md:53 — own design, parity self-pinned; format spec in the
-   *     oracle/dzt.c header comment). */
+   *     oracle/dzt.c header comment).  A DZT file has ONE user-key length
+   *     (1..48 bytes): the entries the job keeps must all share it, whatever
+   *     lengths its inputs hold; otherwise the job fails with status 29 and
+   *     writes no file. */
   uint32_t output_table_factory;
 
   /* Bloom filter build: BlockBasedTableOptions::

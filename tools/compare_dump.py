@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Dev tool: compare a dcw_debug survivor dump (gpurun_out/dbg.{meta,kv})
 against the oracle's output KV stream for the same job (the oracle's output
-files ARE the survivor stream)."""
+files ARE the survivor stream).
+
+`compare_dump.py --npy DIR_A DIR_B` instead compares two
+`bench.py --dump-outputs` directories array by array (two builds run with the
+same arguments); exit status 1 if any array differs."""
 import os
 import struct
 import sys
@@ -31,7 +35,31 @@ def load_dump(prefix):
     return kvs, shared, klen, vlen
 
 
+def compare_npy_dirs(dir_a, dir_b):
+    """Two `bench.py --dump-outputs` directories (two builds, same
+    arguments): every array must be there on both sides and identical.
+    Returns the number of differences."""
+    import numpy as np
+    names_a = sorted(n for n in os.listdir(dir_a) if n.endswith(".npy"))
+    names_b = sorted(n for n in os.listdir(dir_b) if n.endswith(".npy"))
+    bad = 0
+    for n in sorted(set(names_a) ^ set(names_b)):
+        print("ONLY IN ONE:", n)
+        bad += 1
+    for n in sorted(set(names_a) & set(names_b)):
+        a = np.load(os.path.join(dir_a, n))
+        b = np.load(os.path.join(dir_b, n))
+        same = a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b)
+        print("%-28s %-14s %s" % (n, a.shape, "identical" if same else "DIFFER"))
+        bad += not same
+    print("all %d arrays identical" % len(names_a) if bad == 0 and names_a
+          else "dumps DIFFER (%d)" % bad)
+    return bad if names_a else 1
+
+
 def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--npy":
+        sys.exit(1 if compare_npy_dirs(sys.argv[2], sys.argv[3]) else 0)
     prefix = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/dbg"
     oracle_dir = sys.argv[2] if len(sys.argv) > 2 else "/tmp/plan_case/out"
     kvs, shared, klen, vlen = load_dump(prefix)

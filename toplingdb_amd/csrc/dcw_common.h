@@ -36,6 +36,12 @@
 #define DCW_HD static inline
 #endif
 
+// general-key envelope: user keys up to DCW_GKEY_MAX bytes; full keys,
+// boundary keys and range-tombstone starts are kept in side tables of
+// DCW_GKEY_STRIDE-byte rows (dcw_k_decode.h)
+#define DCW_GKEY_MAX 48
+#define DCW_GKEY_STRIDE 48
+
 namespace dcw {
 
 static const uint64_t kMaxSeq = 0x00FFFFFFFFFFFFFFULL; // dbformat.h kMaxSequenceNumber

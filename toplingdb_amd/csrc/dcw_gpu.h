@@ -144,13 +144,17 @@ class GpuJob {
                    std::string* content, uint64_t* n_added, std::string* err);
 
   // ---- range deletions (envelope subset; oracle/compact.c rd_aggr) ----
-  // Fragment list sorted by (normkey, len): frag i covers user keys in
-  // [start_i, start_{i+1}); max_seq 0 marks a gap/terminator.  Set BEFORE
-  // dedup(); the FSM drops covered point keys in its final keep branch.
+  // Fragment list sorted by start key in raw bytewise order (start keys of
+  // any length): frag i covers user keys in [start_i, start_{i+1});
+  // max_seq 0 marks a gap/terminator.  Set BEFORE dedup(); the FSM drops
+  // covered point keys in its final keep branch.
   struct RdFrag {
     uint64_t k0, k1;   // zero-padded big-endian start-key words
-    uint32_t len;      // true byte length (zero-pad tie-break)
+    uint32_t len;      // true byte length
     uint64_t max_seq;
+    // first min(len, DCW_GKEY_MAX) start-key bytes, zero-padded; uploaded in
+    // general-key mode only
+    uint8_t ext[DCW_GKEY_STRIDE];
   };
   void set_range_del_frags(const std::vector<RdFrag>& frags) {
     rd_frags_ = frags;
@@ -186,10 +190,13 @@ class GpuJob {
                       uint64_t total_bytes, uint8_t* host_dst,
                       std::string* err);
   // emit the key area (records per oracle/dzt.c) + per-key-block first
-  // internal keys (stride ukey_len+8) straight into host buffers
+  // internal keys (stride U+8) straight into host buffers.  U = the one
+  // user-key length of the file's survivors: ukey_len in fast mode; in
+  // general-key mode the caller has checked plan_klen() for it (1..48) and
+  // the keys come from the side table.
   int dzt_keyarea(const std::vector<DztKBlock>& kbs,
                   const std::vector<uint32_t>& voff_entry, uint64_t ent_base,
-                  uint64_t key_area_size, uint8_t* host_keyarea,
+                  uint64_t key_area_size, uint32_t U, uint8_t* host_keyarea,
                   uint8_t* host_first_ikeys, std::string* err);
 
   double ms_decode = 0, ms_merge = 0, ms_dedup = 0, ms_emit = 0, ms_h2d = 0,

@@ -410,6 +410,7 @@ struct GpuJob::Impl {
   uint64_t dzt_ccap = 0;
   DevBuf<uint64_t> d_rd_k0, d_rd_k1, d_rd_seq;
   DevBuf<uint32_t> d_rd_len;
+  DevBuf<uint8_t> d_rd_ext; // general-key mode: fragment start bytes
   bool staged_split = false; // stage_begin/chunk in progress
   Event stage_t0;            // recorded by stage_begin
   DevBuf<uint8_t> d_kext;    // general-key side table (48 B/entry full ukeys)
@@ -1245,6 +1246,15 @@ int GpuJob::dedup(const dcw_job_desc* d, std::string* err) {
     P.rd_k1 = p->d_rd_k1;
     P.rd_len = p->d_rd_len;
     P.rd_seq = p->d_rd_seq;
+    if (general_keys) {
+      std::vector<uint8_t> fext((size_t)P.num_rd * DCW_GKEY_STRIDE);
+      for (uint32_t i = 0; i < P.num_rd; i++)
+        memcpy(fext.data() + (size_t)i * DCW_GKEY_STRIDE, rd_frags_[i].ext,
+               DCW_GKEY_STRIDE);
+      HIPCHK(p->d_rd_ext.reserve(fext.size()));
+      HIPCHK(p->h2d_meta(p->d_rd_ext, fext.data(), fext.size()));
+      P.rd_ext = p->d_rd_ext;
+    }
   }
 
   HIPCHK(p->d_survive.reserve(n));
@@ -1871,26 +1881,41 @@ int GpuJob::dzt_pack_values(const std::vector<DztVBlock>& vbs,
 
 int GpuJob::dzt_keyarea(const std::vector<DztKBlock>& kbs,
                         const std::vector<uint32_t>& voff_entry,
-                        uint64_t ent_base, uint64_t key_area_size,
+                        uint64_t ent_base, uint64_t key_area_size, uint32_t U,
                         uint8_t* host_keyarea, uint8_t* host_first_ikeys,
                         std::string* err) {
   Impl* p = p_;
   uint32_t nkb = (uint32_t)kbs.size();
   if (!nkb) return 0;
-  uint32_t ik = ukey_len + 8;
+  if (U < 1 || U > (general_keys ? (uint32_t)DCW_GKEY_MAX : 16u) ||
+      (!general_keys && U != ukey_len)) {
+    if (err) *err = "DZT key emit: user-key length outside envelope";
+    return -1;
+  }
+  uint32_t ik = U + 8;
   HIPCHK(p->d_dzt_kbs.reserve(sizeof(DztKBlock) * nkb));
   HIPCHK(p->d_dzt_keyarea.reserve(key_area_size));
   HIPCHK(p->d_dzt_kidx.reserve((uint64_t)nkb * ik));
   HIPCHK(p->h2d_meta(p->d_dzt_kbs, kbs.data(), sizeof(DztKBlock) * nkb));
   // voff_entry already resident from dzt_values (same file)
   (void)voff_entry;
-  p->kbegin("dzt_keys", 24.0 * (double)nkb * DZTK);
-  hipLaunchKernelGGL(k_dzt_keys, dim3(grid_for(nkb * 64ull)), dim3(64), 0,
-                     p->stream, p->d_dzt_kbs, nkb, p->d_sk0,
-                     p->d_sk1, p->d_stag, p->d_sklen, p->d_sshared,
-                     p->d_dzt_voff, ent_base, p->d_svlen,
-                     ukey_len, p->d_dzt_keyarea,
-                     p->d_dzt_kidx, ik, p->d_err);
+  if (general_keys) {
+    // a record moves its key bytes plus tag, not the fast path's 24
+    p->kbegin("dzt_keys", (double)ik * (double)nkb * DZTK);
+    hipLaunchKernelGGL(k_dzt_keys_g, dim3(grid_for(nkb * 64ull)), dim3(WAVE), 0,
+                       p->stream, p->d_dzt_kbs, nkb, p->d_kext.get(), p->d_sw,
+                       p->d_stag, p->d_sshared, p->d_dzt_voff, ent_base,
+                       p->d_svlen, U, p->d_dzt_keyarea, p->d_dzt_kidx, ik,
+                       p->d_err);
+  } else {
+    p->kbegin("dzt_keys", 24.0 * (double)nkb * DZTK);
+    hipLaunchKernelGGL(k_dzt_keys, dim3(grid_for(nkb * 64ull)), dim3(64), 0,
+                       p->stream, p->d_dzt_kbs, nkb, p->d_sk0,
+                       p->d_sk1, p->d_stag, p->d_sklen, p->d_sshared,
+                       p->d_dzt_voff, ent_base, p->d_svlen,
+                       ukey_len, p->d_dzt_keyarea,
+                       p->d_dzt_kidx, ik, p->d_err);
+  }
   p->kend();
   HIPCHK(hipMemcpyAsync(host_keyarea, p->d_dzt_keyarea, key_area_size,
                         hipMemcpyDeviceToHost, p->stream));

@@ -1,5 +1,6 @@
 // dcw_host.cpp — implementation of dcw_host.h (see header for citations).
 #include "dcw_host.h"
+#include "dcw_dzt_enc.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -773,6 +774,9 @@ std::vector<TombstoneFragment> fragment_tombstones(
                  0, &fr.k0, &fr.k1, &c);
     fr.len = (uint32_t)bounds[i].size();
     fr.max_seq = mx;
+    memset(fr.ext, 0, sizeof(fr.ext));
+    memcpy(fr.ext, bounds[i].data(),
+           std::min<size_t>(bounds[i].size(), DCW_GKEY_MAX));
     frags.push_back(fr);
   }
   return frags;
@@ -809,9 +813,8 @@ std::vector<DztFilePlan> dzt_plan_files(const uint32_t* vlen,
       uint64_t fl = i - fp.first;
       bool opens_key_block = fl % kDztKB == 0;
       if (opens_key_block) fp.kbs.push_back({(uint32_t)i, 0, fp.key_area_size});
-      uint32_t sh = opens_key_block ? 0 : (shared[i] < U ? shared[i] : U);
-      uint32_t ns = U - sh;
-      uint32_t krec = varint_len(sh) + varint_len(ns) + ns + 8 + 4 + 4;
+      uint32_t krec =
+          dzt_krec_size(dzt_krec_shared(shared[i], U, opens_key_block), U);
       fp.kbs.back().count++;
       fp.key_area_size += krec;
       fp.voff.push_back((uint32_t)vb_ulen);

@@ -231,12 +231,15 @@ class FileCutter {
 // ---- range-tombstone fragments ----
 // Fragment i covers user keys in [start_i, start_{i+1}); max_seq 0 marks a
 // gap or the terminator.  Same construction as the oracle's rd_aggr,
-// including the zero-seq gap/terminator fragments; sorted by start key.
-// Bounds must be <= 16 B (the caller checks the envelope).
+// including the zero-seq gap/terminator fragments; sorted by start key in
+// raw bytewise order.  Bounds may have any length: of a start key the device
+// needs the prefix words, the true length and (general-key mode) the first
+// DCW_GKEY_MAX bytes — see bound_cmp (dcw_bound_cmp.h).
 struct TombstoneFragment {
   uint64_t k0, k1; // zero-padded big-endian start-key words
-  uint32_t len;    // true byte length (zero-pad tie-break)
+  uint32_t len;    // true byte length
   uint64_t max_seq;
+  uint8_t ext[DCW_GKEY_STRIDE]; // first min(len, DCW_GKEY_MAX) bytes, 0-padded
 };
 std::vector<TombstoneFragment> fragment_tombstones(
     const std::vector<SstTombstone>& tombstones);
@@ -273,7 +276,8 @@ struct DztFilePlan {
   uint64_t raw_value = 0;
 };
 // vlen / shared: per-survivor value length and internal-key prefix shared
-// with the previous survivor; U = uniform user-key length.
+// with the previous survivor; U = the survivors' one user-key length
+// (1..DCW_GKEY_MAX; the record size rule is dcw_dzt_enc.h's).
 std::vector<DztFilePlan> dzt_plan_files(const uint32_t* vlen,
                                         const uint8_t* shared, size_t nsurv,
                                         uint32_t U, uint64_t target_file_size);

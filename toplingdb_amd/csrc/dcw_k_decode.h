@@ -633,8 +633,7 @@ __global__ void k_decode_entries(
 // user key in a fixed-stride side table `kext` indexed by the entry's
 // payload index w; comparisons gather the tail only on prefix ties
 // (db/dbformat.h:1057-1096 arbitrary-length bytewise contract).
-#define DCW_GKEY_MAX 48
-#define DCW_GKEY_STRIDE 48
+// DCW_GKEY_MAX / DCW_GKEY_STRIDE: dcw_common.h.
 
 // full user-key bytewise compare from the side table (klen = ikey length)
 __device__ __forceinline__ int gkey_cmp(const uint8_t* __restrict__ kext,

@@ -3,6 +3,7 @@
 // dcw_k_*.h headers in order, inside one unit, so every kernel is defined
 // before the host code that launches it.  Not a stand-alone header.
 #pragma once
+#include "dcw_dzt_enc.h"
 
 namespace dcw {
 
@@ -303,6 +304,52 @@ __global__ void k_dzt_keys(const GpuJob::DztKBlock* __restrict__ kbs,
       memcpy(first_ikeys + (uint64_t)kb * ik_stride, key, ik_stride);
     }
     __syncthreads();
+  }
+}
+
+// General-key variant of k_dzt_keys: survivors of one user-key length U in
+// 1..DCW_GKEY_MAX whose key bytes live in the side table kext (row s_w[e]).
+// One wave per key block, one lane per record: the record offsets come from
+// a shuffle scan of the record sizes, and each lane copies its non-shared
+// suffix from the side table straight into the record (dcw_dzt_enc.h) — no
+// private key buffer, so nothing is indexed at run time in scratch.  Lane 0
+// also writes the block's first internal key (U+8 bytes, row stride
+// ik_stride).  Launch with blockDim.x == WAVE.
+__global__ __launch_bounds__(WAVE) void k_dzt_keys_g(
+    const GpuJob::DztKBlock* __restrict__ kbs, uint32_t nkb,
+    const uint8_t* __restrict__ kext, const uint32_t* __restrict__ s_w,
+    const uint64_t* __restrict__ s_tag, const uint8_t* __restrict__ s_sshared,
+    const uint32_t* __restrict__ voff_entry, uint64_t ent_base,
+    const uint32_t* __restrict__ s_vlen, uint32_t ukey_len,
+    uint8_t* __restrict__ keyarea, uint8_t* __restrict__ first_ikeys,
+    uint32_t ik_stride, uint32_t* err_flag) {
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t kb = blockIdx.x; kb < nkb; kb += gridDim.x) {
+    GpuJob::DztKBlock K = kbs[kb];
+    if (K.count > DZTK || blockDim.x != WAVE) { // uniform across the wave
+      if (lane == 0) set_err(err_flag, DE_BLOCK_PARSE);
+      continue;
+    }
+    const bool act = lane < K.count;
+    const uint64_t e = K.first + (act ? lane : 0);
+    uint32_t sh = dzt_krec_shared(s_sshared[e], ukey_len, lane == 0);
+    uint32_t sz = act ? dzt_krec_size(sh, ukey_len) : 0;
+    uint32_t inc = sz;
+    for (int d = 1; d < WAVE; d <<= 1) {
+      uint32_t x = __shfl_up(inc, d);
+      if ((int)lane >= d) inc += x;
+    }
+    if (act) { // no early continue: the wave meets whole at the next scan
+      const uint8_t* ukey = kext + (uint64_t)s_w[e] * DCW_GKEY_STRIDE;
+      uint64_t tag = s_tag[e];
+      dzt_krec_put(keyarea + K.koff + (inc - sz), sh, ukey_len, ukey, tag,
+                   voff_entry[e - ent_base], s_vlen[e]);
+      if (lane == 0) {
+        uint8_t* fk = first_ikeys + (uint64_t)kb * ik_stride;
+        dzt_copy_bytes(fk, ukey, ukey_len);
+        store64(fk + ukey_len, tag);
+      }
+    }
   }
 }
 

@@ -3,6 +3,7 @@
 // dcw_k_*.h headers in order, inside one unit, so every kernel is defined
 // before the host code that launches it.  Not a stand-alone header.
 #pragma once
+#include "dcw_bound_cmp.h"
 
 namespace dcw {
 
@@ -175,28 +176,24 @@ struct FsmParams {
   const uint64_t* rd_k0;
   const uint64_t* rd_k1;
   const uint32_t* rd_len;
+  const uint8_t* rd_ext; // general-key mode only, like lb_sm_ext
   const uint64_t* rd_seq;
   uint32_t num_rd;
   uint32_t rd_ukey_len; // the job's uniform user-key length
 };
 
 // covered iff the fragment containing the user key has max_seq > seq
-// (range_del_aggregator.cc:407-413 single-stripe rule; zero-padded
-// normkey compare with byte-length tie-break == raw bytewise order)
+// (range_del_aggregator.cc:407-413 single-stripe rule).  The fragment is
+// found in raw bytewise order through bound_cmp (dcw_bound_cmp.h, where the
+// argument for the search staying monotone on starts it cannot tell apart
+// is written down).  w: payload index of the group's first entry.
 __device__ __forceinline__ bool fsm_rd_covers(const FsmParams& P, uint64_t k0,
-                                              uint64_t k1, uint64_t seq) {
-  uint32_t lo = 0, hi = P.num_rd;
-  while (lo < hi) { // last frag with (k0,k1,len) <= (key, ukey_len)
-    uint32_t mid = (lo + hi) / 2;
-    bool le = P.rd_k0[mid] < k0 ||
-              (P.rd_k0[mid] == k0 &&
-               (P.rd_k1[mid] < k1 ||
-                (P.rd_k1[mid] == k1 && P.rd_len[mid] <= P.rd_ukey_len)));
-    if (le)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
+                                              uint64_t k1, uint64_t w,
+                                              uint64_t seq) {
+  const uint8_t* kfull = P.kext ? P.kext + w * DCW_GKEY_STRIDE : nullptr;
+  uint32_t ulen = P.kext ? (uint32_t)P.klen[w] - 8 : P.rd_ukey_len;
+  uint32_t lo = rd_frag_upper(P.rd_k0, P.rd_k1, P.rd_len, P.rd_ext, P.num_rd,
+                              k0, k1, ulen, kfull);
   if (lo == 0) return false;
   return P.rd_seq[lo - 1] > seq;
 }
@@ -213,32 +210,6 @@ __device__ uint64_t fsm_find_earliest(const FsmParams& P, uint64_t seq,
   }
   *prev = lo > 0 ? P.snapshots[lo - 1] : 0;
   return lo < P.num_snapshots ? P.snapshots[lo] : kMaxSeq;
-}
-
-// Raw bytewise order (Compare(bound, key) of the bytewise comparator) of a
-// boundary user key of ANY length against a job key: <0, 0, >0.
-// (b0,b1) / (k0,k1) are the zero-padded 16-byte prefix words.  Where they
-// differ the first differing byte decides, as in raw order (a pad byte only
-// meets a real byte when the shorter key is a prefix of the longer, and 0 is
-// the smallest byte).  Where they tie, fast mode (kfull null, ulen <= 16)
-// breaks the tie on length exactly as fsm_rd_covers does; general mode
-// compares the stored bytes first.  bext holds min(blen, DCW_GKEY_MAX)
-// bytes: a job key is at most DCW_GKEY_MAX long, so of a longer boundary
-// only that prefix and "it is longer" matter.
-__device__ __forceinline__ int bound_cmp(uint64_t b0, uint64_t b1, uint32_t blen,
-                                         const uint8_t* __restrict__ bext,
-                                         uint64_t k0, uint64_t k1, uint32_t ulen,
-                                         const uint8_t* __restrict__ kfull) {
-  if (b0 != k0) return b0 < k0 ? -1 : 1;
-  if (b1 != k1) return b1 < k1 ? -1 : 1;
-  if (kfull) {
-    uint32_t m = blen < DCW_GKEY_MAX ? blen : DCW_GKEY_MAX;
-    if (ulen < m) m = ulen;
-    for (uint32_t t = 0; t < m; t++)
-      if (bext[t] != kfull[t]) return bext[t] < kfull[t] ? -1 : 1;
-  }
-  if (blen != ulen) return blen < ulen ? -1 : 1;
-  return 0;
 }
 
 // w: payload index of the group's first entry (general mode: its full key)
@@ -383,7 +354,7 @@ __global__ void k_group_fsm(const ulong4* __restrict__ e, uint64_t n,
         } else {
           consumed = g1 - pos; // drop delete and all covered versions
         }
-      } else if (P.num_rd && fsm_rd_covers(P, k0, k1, seq)) {
+      } else if (P.num_rd && fsm_rd_covers(P, k0, k1, e[g0].w, seq)) {
         // dropped by a range tombstone (compaction_iterator.cc:1056-1063:
         // the ShouldDelete site is the final keep branch only)
       } else {

@@ -602,11 +602,11 @@ int acquire_inputs(JobCtx& c) {
       return fail(c.res, 29,
                   "range deletions outside supported envelope "
                   "(bottommost, no snapshots, no grandparents)");
-    for (auto& t : *c.tombstones)
-      if (t.start.size() > 16 || t.end.size() > 16)
-        return fail(c.res, 29, "range tombstone bound exceeds 16 B envelope");
-    for (auto& f : fragment_tombstones(*c.tombstones))
-      c.rd_frags.push_back({f.k0, f.k1, f.len, f.max_seq});
+    for (auto& f : fragment_tombstones(*c.tombstones)) {
+      GpuJob::RdFrag r{f.k0, f.k1, f.len, f.max_seq, {0}};
+      memcpy(r.ext, f.ext, sizeof(r.ext));
+      c.rd_frags.push_back(r);
+    }
   }
   return 0;
 }
@@ -634,15 +634,12 @@ int run_front(JobCtx& c) {
     c.wp.mark(kWpDecode);
   }
   if (job.general_keys) {
-    // general-key mode envelope: these combinations still fall back local
-    if (!c.rd_frags.empty())
-      return fail(c.res, 29, "range deletions with general-shape keys "
-                             "outside envelope");
+    // general-key mode envelope: this combination still falls back local.
+    // (DcwZipTable output needs one user-key length over the SURVIVORS,
+    // which only dedup knows: dzt_finish checks it.)
     if (d->num_grandparents > 0)
       return fail(c.res, 29, "grandparent cutting with general-shape keys "
                              "outside envelope");
-    if (d->output_table_factory == 1)
-      return fail(c.res, 29, "DcwZipTable requires uniform user-key length");
   }
   if (job.merge(&err) != 0) return fail(c.res, 19, err);
   c.wp.mark(kWpMerge);
@@ -1190,13 +1187,12 @@ std::string build_dzt_props_footer(const TableOpts& o, const DztFilePlan& fp,
 // Builds one DZT file image on the GPU and the host, starts its write in
 // the background (dzt_writes) and fills the file's meta.
 int build_dzt_file(JobCtx& c, const DztFilePlan& fp, const TableOpts& o,
-                   DztProf& prof,
+                   uint32_t U, DztProf& prof,
                    std::vector<std::future<bool>>& dzt_writes,
                    dcw_output_file* of) {
   GpuJob& job = c.job;
   std::string err;
-  const uint32_t U = job.ukey_len;
-  const uint32_t IK = U + 8;
+  const uint32_t IK = U + 8; // <= 56: fits the 64-byte ABI key fields
   std::vector<GpuJob::DztVBlock> vbs;
   std::vector<GpuJob::DztKBlock> kbs;
   for (auto& v : fp.vbs) vbs.push_back({v.first, v.count, v.ulen, v.stage_off});
@@ -1230,7 +1226,7 @@ int build_dzt_file(JobCtx& c, const DztFilePlan& fp, const TableOpts& o,
   std::vector<uint8_t> first_ikeys((uint64_t)nkb * IK);
   image.reserve(lay.props_off + (64u << 10)); // props+footer appended after
   image.resize_uninit(lay.props_off);
-  if (job.dzt_keyarea(kbs, fp.voff, fp.first, fp.key_area_size, image.p,
+  if (job.dzt_keyarea(kbs, fp.voff, fp.first, fp.key_area_size, U, image.p,
                       first_ikeys.data(), &err) != 0)
     return fail(c.res, 33, err);
   prof.mark(kDztKeyArea);
@@ -1310,9 +1306,26 @@ int build_dzt_file(JobCtx& c, const DztFilePlan& fp, const TableOpts& o,
 int dzt_finish(JobCtx& c) {
   const dcw_job_desc* d = c.d;
   GpuJob& job = c.job;
+  // The format has one user-key length U per file and the oracle's builder
+  // takes it from the survivors (orc_dzt_builder_add), not from the inputs.
+  // Fast mode: the job's uniform length.  General-key mode: the survivors'
+  // lengths (plan metadata) must all be equal — any U in 1..48 then.
+  uint32_t U = job.ukey_len;
+  if (job.general_keys) {
+    const std::vector<uint8_t>& klen = job.plan_klen();
+    for (size_t i = 1; i < job.num_survivors(); i++)
+      if (klen[i] != klen[0])
+        return fail(c.res, 29, "DcwZipTable requires uniform user-key length");
+    if (job.num_survivors()) U = (uint32_t)klen[0] - 8;
+    // the decoders refuse empty user keys (klen < 9) before this; should one
+    // ever get here, refuse it as an envelope matter, not in the key emit
+    if (job.num_survivors() && U == 0)
+      return fail(c.res, 29, "DcwZipTable requires a user-key length of "
+                             "1..48 (outside envelope)");
+  }
   std::vector<DztFilePlan> files =
       dzt_plan_files(job.plan_vlen().data(), job.plan_shared().data(),
-                     job.num_survivors(), job.ukey_len, d->target_file_size);
+                     job.num_survivors(), U, d->target_file_size);
   TableOpts o = opts_from_desc(d);
   uint64_t next_file_number = d->next_file_number;
   std::vector<dcw_output_file> out_files;
@@ -1323,7 +1336,7 @@ int dzt_finish(JobCtx& c) {
     prof.t_last = now_usec();
     o.orig_file_number = next_file_number++;
     dcw_output_file of;
-    if (int rc = build_dzt_file(c, fp, o, prof, dzt_writes, &of)) return rc;
+    if (int rc = build_dzt_file(c, fp, o, U, prof, dzt_writes, &of)) return rc;
     out_files.push_back(of);
     total_out_bytes += of.file_size;
     total_out_entries += fp.count;
