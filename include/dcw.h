@@ -46,6 +46,13 @@ enum {
                                  load (util/compression.h:1332 framing:
                                  varint32 decompressed size + zstd frame);
                                  output compression stays none/snappy */
+  DCW_COMPRESSION_LZ4 = 0x4,  /* INPUT blocks only, as LZ4HC: varint32 */
+  DCW_COMPRESSION_LZ4HC = 0x5, /* decompressed size + one raw LZ4 block
+                                 (util/compression.h LZ4_Uncompress,
+                                 compress_format_version 2), decoded on the
+                                 GPU (k_decompress_lz4).  Blocks coded with a
+                                 preset dictionary (a file whose metaindex
+                                 names rocksdb.compression_dict) are refused */
 };
 
 /* ChecksumType (include/rocksdb/table.h; default kXXH3, table.h:257) */

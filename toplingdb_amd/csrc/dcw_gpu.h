@@ -41,6 +41,10 @@ struct GpuInputs {
   std::vector<BlockRef> blocks;         // grouped by run, run-major order
   std::vector<uint32_t> run_block_begin; // size num_runs+1
   std::vector<DztFileRef> dzt_files;     // run-major file order
+  // indices into `blocks` of the LZ4/LZ4HC blocks (trailer type 4 or 5),
+  // ascending, and their stored bytes: k_decompress_lz4's work list
+  std::vector<uint32_t> lz4_blocks;
+  uint64_t lz4_stored_bytes = 0;
   uint32_t checksum_type = 4;
 };
 
@@ -54,6 +58,8 @@ struct StagedInput {
   uint32_t checksum_type = 4;
   std::vector<uint32_t> run_block_begin;
   std::vector<DztFileRef> dzt_files; // host tables of the DZT files in d_blob
+  std::vector<uint32_t> lz4_blocks;  // as GpuInputs
+  uint64_t lz4_stored_bytes = 0;
   ~StagedInput();
 };
 
@@ -218,6 +224,8 @@ class GpuJob {
   std::vector<uint32_t> h_vlen_;
   std::vector<uint32_t> run_blocks_;
   std::vector<DztFileRef> dzt_files_; // DZT inputs of the staged job
+  std::vector<uint32_t> lz4_blocks_;  // LZ4 blocks of the staged job
+  uint64_t lz4_stored_bytes_ = 0;
   // DZT branch of decode(): table upload, and the key-block decode
   int dzt_upload_tables(std::string* err);
   int dzt_decode_keys(bool general, std::string* err);

@@ -345,6 +345,7 @@ struct GpuJob::Impl {
   // decode
   DevBuf<uint32_t> d_usize;
   DevBuf<uint8_t> d_btype_in;
+  DevBuf<uint32_t> d_lz4idx; // LZ4/LZ4HC input blocks (k_decompress_lz4)
   DevBuf<uint64_t> d_uoff;
   DevBuf<uint8_t> d_ublob;
   uint64_t ublob_size = 0;
@@ -468,6 +469,8 @@ struct GpuJob::Impl {
     if (code) *code = e;
     if (e && what) {
       if (err) *err = std::string(what) + " failed, code " + std::to_string(e);
+      if (err && e == DE_LZ4)
+        *err += " (DE_LZ4: bad LZ4/LZ4HC preamble or stream in an input block)";
       return -1;
     }
     return 0;
@@ -534,6 +537,8 @@ void GpuJob::reset() {
   h_vlen_.clear();
   run_blocks_.clear();
   dzt_files_.clear();
+  lz4_blocks_.clear();
+  lz4_stored_bytes_ = 0;
   rd_frags_.clear();
   ms_decode = ms_merge = ms_dedup = ms_emit = ms_h2d = ms_d2h = 0;
 }
@@ -613,6 +618,8 @@ int GpuJob::stage(const GpuInputs& in, std::string* err) {
   // remember run boundaries (translated to entries later)
   run_blocks_ = in.run_block_begin;
   dzt_files_ = in.dzt_files;
+  lz4_blocks_ = in.lz4_blocks;
+  lz4_stored_bytes_ = in.lz4_stored_bytes;
   return 0;
 }
 
@@ -631,6 +638,8 @@ int GpuJob::stage_adopt(const StagedInput& s, std::string* err) {
   p->checksum_type = s.checksum_type;
   run_blocks_ = s.run_block_begin;
   dzt_files_ = s.dzt_files;
+  lz4_blocks_ = s.lz4_blocks;
+  lz4_stored_bytes_ = s.lz4_stored_bytes;
   if (p->arm_consts(err) != 0) return -1;
   HIPCHK(hipStreamSynchronize(p->stream));
   return 0;
@@ -648,6 +657,8 @@ int GpuJob::stage_release(StagedInput* s, std::string* err) {
   s->checksum_type = p->checksum_type;
   s->run_block_begin = run_blocks_;
   s->dzt_files = dzt_files_;
+  s->lz4_blocks = lz4_blocks_;
+  s->lz4_stored_bytes = lz4_stored_bytes_;
   return 0;
 }
 
@@ -723,6 +734,19 @@ int GpuJob::decode(std::string* err) {
                        p->d_err, dec_pipe);
   }
   p->kend();
+  if (!lz4_blocks_.empty()) {
+    // LZ4/LZ4HC blocks, which k_decompress skipped: one wave per listed block
+    uint32_t nl = (uint32_t)lz4_blocks_.size();
+    double decoded = 0;
+    for (uint32_t b : lz4_blocks_) decoded += usize[b];
+    HIPCHK(p->d_lz4idx.reserve(sizeof(uint32_t) * nl));
+    HIPCHK(p->h2d_meta(p->d_lz4idx, lz4_blocks_.data(), sizeof(uint32_t) * nl));
+    p->kbegin("decompress_lz4", (double)lz4_stored_bytes_ + decoded);
+    hipLaunchKernelGGL(k_decompress_lz4, dim3(grid_for(nl * 64ull)), dim3(256), 0,
+                       p->stream, p->d_blob, p->d_boff, p->d_bsize, p->d_uoff,
+                       p->d_usize, p->d_lz4idx, nl, p->d_ublob, p->d_err);
+    p->kend();
+  }
   if (n_dvb) {
     double stored = 0;
     for (auto& v : p->h_dzi_vbs) stored += v.csize;

@@ -1,6 +1,7 @@
 // dcw_host.cpp — implementation of dcw_host.h (see header for citations).
 #include "dcw_host.h"
 #include "dcw_dzt_enc.h"
+#include "dcw_lz4_dec.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -288,6 +289,20 @@ ParsedSst parse_sst(const uint8_t* data, size_t size) {
     }
     ib = (const uint8_t*)dec.data();
     idx_sz = ul;
+  } else if (type == 4 || type == 5) { // LZ4 / LZ4HC: the data blocks' decoder
+    uint32_t ul;
+    int hn = lz4_preamble(ib, (uint32_t)idx_sz, &ul);
+    if (hn < 0 || (ul >> 31) || idx_sz > 0x7fffffffu) {
+      r.error = "index lz4 preamble";
+      return r;
+    }
+    dec.resize(ul);
+    if (!lz4_dec(ib + hn, (uint32_t)idx_sz - hn, (uint8_t*)dec.data(), ul)) {
+      r.error = "index lz4 corrupt";
+      return r;
+    }
+    ib = (const uint8_t*)dec.data();
+    idx_sz = ul;
   } else if (type != 0) {
     r.error = "index compression unsupported";
     return r;
@@ -352,6 +367,12 @@ ParsedSst parse_sst(const uint8_t* data, size_t size) {
         mkey.resize(sh);
         mkey.append((const char*)mp, ns);
         mp += ns;
+        if (mkey == "rocksdb.compression_dict") {
+          // blocks coded against a preset dictionary: no decoder here has it
+          r.error = "dictionary-compressed blocks (rocksdb.compression_dict) "
+                    "unsupported";
+          return r;
+        }
         if (mkey == "rocksdb.range_del") {
           const uint8_t* vp = mp;
           int b1 = varint64_get(vp, mp + vl, &rd_off);

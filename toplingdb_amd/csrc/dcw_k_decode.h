@@ -4,6 +4,7 @@
 // before the host code that launches it.  Not a stand-alone header.
 #pragma once
 #include "dcw_gpu.h"
+#include "dcw_lz4_dec.h"
 
 #define WAVE 64
 
@@ -19,6 +20,7 @@ enum DevErr : uint32_t {
   DE_SD_CONTRACT = 6,  // SingleDelete + Delete mix (Corruption in reference)
   DE_COMPRESS_TYPE = 7,
   DE_PLAN_WIDTH = 8,   // planned block exceeds the emit kernel's entry bound
+  DE_LZ4 = 9,          // LZ4/LZ4HC input block: bad preamble or stream
 };
 
 // ------------------------------------------------------------------
@@ -67,6 +69,13 @@ __global__ void k_verify_usize(const uint8_t* __restrict__ blob,
         return;
       }
       usize[i] = (uint32_t)ul;
+    } else if (type == 4 || type == 5) { // LZ4 / LZ4HC: varint32 preamble
+      uint32_t ul;
+      if (lz4_preamble(p, sz, &ul) < 0) {
+        set_err(err_flag, DE_LZ4);
+        return;
+      }
+      usize[i] = ul;
     } else {
       set_err(err_flag, DE_COMPRESS_TYPE);
       return;
@@ -262,6 +271,7 @@ __global__ __launch_bounds__(256) void k_decompress(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
+    } else if (btype[i] != 1) { // type 4 or 5: k_decompress_lz4's block
     } else if (n <= DEC_MAX && usize[i] <= DEC_MAX) {
       // 16-byte staging: byte-granular copies issued ~5000 DS ops per
       // block per wave and saturated the CU's DS issue pipe that the 16
@@ -334,6 +344,7 @@ __global__ __launch_bounds__(256) void k_decompress_v1(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
+    } else if (btype[i] != 1) { // type 4 or 5: k_decompress_lz4's block
     } else if (usize[i] <= DEC_MAX) {
       if (lane == 0) {
         if (snappy_uncompress(src, n, L.out, usize[i]) != usize[i])
@@ -380,9 +391,69 @@ __global__ __launch_bounds__(256) void k_decompress_v2(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
+    } else if (btype[i] != 1) { // type 4 or 5: k_decompress_lz4's block
     } else if (lane == 0) {
       if (snappy_uncompress(src, n, dst, usize[i]) != usize[i])
         set_err(err_flag, DE_SNAPPY);
+    }
+  }
+}
+
+// LZ4 / LZ4HC input blocks (types 4 and 5), one wave per block over the
+// host-built list of their indices (`list`, as k_compress_large's): a job
+// without such blocks never launches this.  Same geometry as k_decompress:
+// the stream and the decoded block are both staged in LDS with 16-byte
+// cooperative copies, lane 0 runs the serial register-window decoder.  A
+// block beyond DEC_MAX on either side is decoded global to global by
+// lane 0.  The wave-parallel decode schemes measured for snappy
+// have the same dependency structure here and are not repeated.
+__global__ __launch_bounds__(256) void k_decompress_lz4(
+    const uint8_t* __restrict__ blob, const uint64_t* __restrict__ boff,
+    const uint32_t* __restrict__ bsize, const uint64_t* __restrict__ uoff,
+    const uint32_t* __restrict__ usize, const uint32_t* __restrict__ list,
+    uint32_t nlist, uint8_t* __restrict__ ublob, uint32_t* err_flag) {
+  __shared__ DecLds lds[4];
+  uint32_t waves_per_wg = blockDim.x / WAVE;
+  uint32_t wid = threadIdx.x / WAVE;
+  uint32_t wave = blockIdx.x * waves_per_wg + wid;
+  uint32_t lane = threadIdx.x % WAVE;
+  uint32_t stride = gridDim.x * waves_per_wg;
+  DecLds& L = lds[wid];
+  for (uint32_t li = wave; li < nlist; li += stride) {
+    uint32_t i = list[li];
+    const uint8_t* src = blob + boff[i];
+    uint8_t* dst = ublob + uoff[i];
+    uint32_t un = usize[i];
+    // the preamble again (k_verify_usize accepted it): 1..5 bytes
+    uint32_t hn = 1;
+    while (hn < 5 && (src[hn - 1] & 0x80)) hn++;
+    src += hn;
+    uint32_t n = bsize[i] - hn;
+    if (n <= DEC_MAX && un <= DEC_MAX) {
+      // the stream starts behind the preamble, so it is not 16-byte aligned
+      // in the blob: the loads are unaligned global loads, the LDS side of
+      // every copy is aligned
+      for (uint32_t t = lane * 16; t + 16 <= n; t += WAVE * 16) {
+        ulong2 v;
+        memcpy(&v, src + t, 16);
+        memcpy(L.in + t, &v, 16);
+      }
+      if (lane == 0)
+        for (uint32_t t = n & ~15u; t < n; t++) L.in[t] = src[t];
+      wave_lds_sync2();
+      if (lane == 0 && !lz4_dec_lds(L.in, n, L.out, un))
+        set_err(err_flag, DE_LZ4);
+      wave_lds_sync2();
+      for (uint32_t t = lane * 16; t + 16 <= un; t += WAVE * 16) {
+        ulong2 v;
+        memcpy(&v, L.out + t, 16);
+        memcpy(dst + t, &v, 16);
+      }
+      if (lane == 0)
+        for (uint32_t t = un & ~15u; t < un; t++) dst[t] = L.out[t];
+      wave_lds_sync2();
+    } else if (lane == 0) {
+      if (!lz4_dec(src, n, dst, un)) set_err(err_flag, DE_LZ4);
     }
   }
 }

@@ -434,11 +434,19 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
   bool any_zstd = false;
   uint32_t ct = cstype == 0xffffffff ? 4 : cstype;
   tphase = now_usec();
-  for (auto& blk : L->gi.blocks)
-    if (L->blob.p[blk.off + blk.size] == 7) {
+  // the same walk lists the LZ4 / LZ4HC blocks (types 4 and 5) for
+  // k_decompress_lz4; the rewrite below keeps block order and copies
+  // non-zstd blocks verbatim, so the indices hold either way
+  for (size_t bi = 0; bi < L->gi.blocks.size(); bi++) {
+    const BlockRef& blk = L->gi.blocks[bi];
+    uint8_t type = L->blob.p[blk.off + blk.size];
+    if (type == 7) {
       any_zstd = true;
-      break;
+    } else if (type == 4 || type == 5) {
+      L->gi.lz4_blocks.push_back((uint32_t)bi);
+      L->gi.lz4_stored_bytes += blk.size;
     }
+  }
   L->us_parse += now_usec() - tphase;
   if (any_zstd && !L->gi.dzt_files.empty()) {
     // the rewrite below rebuilds the blob from BlockBasedTable blocks alone
