@@ -45,14 +45,18 @@ enum {
   DCW_COMPRESSION_ZSTD = 0x7, /* INPUT blocks only: decoded host-side at
                                  load (util/compression.h:1332 framing:
                                  varint32 decompressed size + zstd frame);
-                                 output compression stays none/snappy */
-  DCW_COMPRESSION_LZ4 = 0x4,  /* INPUT blocks only, as LZ4HC: varint32 */
+                                 refused as output compression */
+  DCW_COMPRESSION_LZ4 = 0x4,  /* input and output, as LZ4HC: varint32 */
   DCW_COMPRESSION_LZ4HC = 0x5, /* decompressed size + one raw LZ4 block
                                  (util/compression.h LZ4_Uncompress,
-                                 compress_format_version 2), decoded on the
-                                 GPU (k_decompress_lz4).  Blocks coded with a
-                                 preset dictionary (a file whose metaindex
-                                 names rocksdb.compression_dict) are refused */
+                                 compress_format_version 2).  Decoded on the
+                                 GPU (k_decompress_lz4) and encoded there
+                                 (k_compress_lz4; one encoder, the two differ
+                                 in the block type byte only).  Blocks coded
+                                 with a preset dictionary (a file whose
+                                 metaindex names rocksdb.compression_dict)
+                                 are refused; so is LZ4 output together with
+                                 output_table_factory = 1 */
 };
 
 /* ChecksumType (include/rocksdb/table.h; default kXXH3, table.h:257) */

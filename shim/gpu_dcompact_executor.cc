@@ -203,7 +203,8 @@ class DcwGpuCompactionExecutor : public CompactionExecutor {
       return Status::NotSupported("merge operator");
     if (!p.compaction_filter_factory.clazz.empty())
       return Status::NotSupported("compaction filter");
-    if (p.compression != kNoCompression && p.compression != kSnappyCompression)
+    if (p.compression != kNoCompression && p.compression != kSnappyCompression &&
+        p.compression != kLZ4Compression && p.compression != kLZ4HCCompression)
       return Status::NotSupported("compression type");
 
     // input file path: cf_paths[path_id] + %06llu.sst (MakeTableFileName)
@@ -243,8 +244,10 @@ class DcwGpuCompactionExecutor : public CompactionExecutor {
     d->cf_name = p.cf_name.c_str();
     d->output_level = p.output_level;
     d->bottommost_level = p.bottommost_level ? 1 : 0;
-    d->compression = p.compression == kSnappyCompression
-                         ? DCW_COMPRESSION_SNAPPY
+    d->compression = p.compression == kSnappyCompression ? DCW_COMPRESSION_SNAPPY
+                     : p.compression == kLZ4Compression  ? DCW_COMPRESSION_LZ4
+                     : p.compression == kLZ4HCCompression
+                         ? DCW_COMPRESSION_LZ4HC
                          : DCW_COMPRESSION_NONE;
     d->target_file_size = p.target_file_size;
     d->max_compaction_bytes = p.max_compaction_bytes;

@@ -1415,10 +1415,11 @@ int GpuJob::emit_blocks(const std::vector<PlannedBlock>& blocks, const TableOpts
   uint64_t last = blocks.back().first + blocks.back().count;
   uint64_t nent = last - first;
   (void)nent;
-  // descs: raw-image offsets (uout) and, for snappy output, every block's
-  // own compressed-output slot (cout): a running sum of worst-case encoder
-  // sizes, so one huge block does not size every slot of the chunk.  Blocks
-  // over SNAP_MAX_UNC are listed for k_compress_large.
+  // descs: raw-image offsets (uout) and, for snappy or LZ4 output, every
+  // block's own compressed-output slot (cout): a running sum of worst-case
+  // encoder sizes, so one huge block does not size every slot of the chunk.
+  // Snappy blocks over SNAP_MAX_UNC are listed for k_compress_large.
+  const bool lz4_out = o.compression == 4 || o.compression == 5;
   std::vector<EmitBlockDesc> bds(nb);
   std::vector<uint32_t> big;
   uint64_t uout = 0, cslot = 0;
@@ -1437,6 +1438,15 @@ int GpuJob::emit_blocks(const std::vector<PlannedBlock>& blocks, const TableOpts
       }
       cslot += (snappy_max_compressed(pb.unc_size) + 63) & ~(uint64_t)63;
       if (pb.unc_size > SNAP_MAX_UNC) big.push_back(b);
+    } else if (lz4_out) {
+      if (pb.unc_size > kLz4MaxUnc) {
+        if (err)
+          *err = "data block of " + std::to_string(pb.unc_size) +
+                 " B is past the LZ4 encoder's 2 GiB bound; job outside "
+                 "envelope";
+        return -1;
+      }
+      cslot += (5 + lz4_max_compressed(pb.unc_size) + 63) & ~(uint64_t)63;
     }
   }
   p->emit_base = first;
@@ -1496,6 +1506,15 @@ int GpuJob::emit_blocks(const std::vector<PlannedBlock>& blocks, const TableOpts
                          p->d_err);
       p->kend();
     }
+  } else if (lz4_out) {
+    HIPCHK(p->d_cblob.reserve(cslot));
+    p->kbegin("compress_lz4", 2.6 * (double)uout); // two read passes
+    uint32_t cgrid = (nb + 3) / 4;
+    hipLaunchKernelGGL(k_compress_lz4, dim3(cgrid < 4096 ? cgrid : 4096),
+                       dim3(256), 0, p->stream, p->d_bds, nb, p->d_ucblob,
+                       p->d_cblob, p->d_ebsize, p->d_ebtype,
+                       (uint8_t)o.compression, p->d_err);
+    p->kend();
   } else {
     hipLaunchKernelGGL(k_sizes_nocomp, dim3(grid_for(nb)), dim3(256), 0,
                        p->stream, p->d_bds, nb, p->d_ebsize, p->d_ebtype);

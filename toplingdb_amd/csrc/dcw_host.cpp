@@ -2,6 +2,7 @@
 #include "dcw_host.h"
 #include "dcw_dzt_enc.h"
 #include "dcw_lz4_dec.h"
+#include "dcw_lz4_enc.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -438,6 +439,15 @@ SstIndexEntry append_block(std::string& out, const TableOpts& o,
       bn = cn;
       type = 1;
     }
+  } else if (try_compress && (o.compression == 4 || o.compression == 5) &&
+             n <= kLz4MaxUnc) {
+    comp.resize(5 + lz4_max_compressed(n));
+    size_t cn = lz4_encode_block(data, (uint32_t)n, (uint8_t*)comp.data());
+    if (cn <= ((uint64_t)896 * n) >> 10) { // the same rule as snappy
+      body = (const uint8_t*)comp.data();
+      bn = cn;
+      type = (uint8_t)o.compression;
+    }
   }
   SstIndexEntry h{out.size(), bn};
   out.append((const char*)body, bn);
@@ -523,7 +533,10 @@ std::string build_tail(const TableOpts& o, const TailStats& st,
   adds("rocksdb.prefix.extractor.name", "nullptr");
   adds("rocksdb.property.collectors", "[]");
   if (!o.cf_name.empty()) adds("rocksdb.column.family.name", o.cf_name);
-  adds("rocksdb.compression", o.compression == 1 ? "Snappy" : "NoCompression");
+  adds("rocksdb.compression", o.compression == 1   ? "Snappy"
+                              : o.compression == 4 ? "LZ4"
+                              : o.compression == 5 ? "LZ4HC"
+                                                   : "NoCompression");
   adds("rocksdb.compression_options",
        "window_bits=-14; level=32767; strategy=0; max_dict_bytes=0; "
        "zstd_max_train_bytes=0; enabled=0; max_dict_buffer_bytes=0; "

@@ -3,6 +3,7 @@
 // dcw_k_*.h headers in order, inside one unit, so every kernel is defined
 // before the host code that launches it.  Not a stand-alone header.
 #pragma once
+#include "dcw_lz4_enc.h"
 #include "dcw_snap_enc_big.h"
 
 namespace dcw {
@@ -626,6 +627,192 @@ __global__ __launch_bounds__(256) void k_compress_large(
       btype[b] = 0;
     }
     wave_lds_sync();
+  }
+}
+
+// ---- LZ4 / LZ4HC output (codec and seam rule: dcw_lz4_enc.h) ----
+// One wave per block of any size below 2^31, 4 waves per workgroup, a u16
+// min-position table of 4 KiB per wave.  The block is taken window by window
+// (65536 bytes; a default block is one window) in two passes.  Pass 1
+// measures: per window the table, the 64 lane summaries, the seam scan and a
+// prefix sum of lz4_lane_bytes; the running literal carry and output offset
+// pass on to the next window.  The ratio test is lane-uniform arithmetic on
+// the measured total; a rejected block stores nothing.  Pass 2 writes: a
+// one-window block still holds its table and plan, a larger one rebuilds
+// them per window.  Each lane writes its own bytes (lz4_emit_lane), the
+// window's first lane with a match writes the head of the sequence that it
+// closes, and the literals carried in from earlier windows, like the final
+// literal-only sequence, are copied by all lanes together.
+// Writes stay inside the slot: pass 2 runs only when hl + total <=
+// (896*n) >> 10 < n, the slot holds 5 + lz4_max_compressed(n) > n bytes, and
+// every lane writes exactly the bytes that the prefix sum gave it.
+struct Lz4WavePlan {
+  Lz4Seg r;  // this lane's segment [s0, s1)
+  uint32_t s0, s1, later, lnext, nibnext, at;
+  // lane-uniform: lanes with a match, the first of them and the sequence it
+  // closes, where that sequence starts, the literals carried into the window
+  uint64_t hasmask;
+  uint32_t f0, l0, nib0, head_at, cin;
+};
+
+__device__ __forceinline__ void lz4_wave_table(const uint8_t* __restrict__ in,
+                                               uint32_t base, uint32_t wend,
+                                               uint16_t* tab, uint32_t lane) {
+  wave_lds_sync(); // the walks of the window before are done with the table
+  uint32_t* tw = (uint32_t*)tab;
+  for (uint32_t t = lane; t < (1u << kSnapHashBits) / 2; t += WAVE)
+    tw[t] = 0xffffffffu;
+  wave_lds_sync();
+  for (uint32_t p = base + lane; p + 4 <= wend; p += WAVE) {
+    uint32_t h = (load32(in + p) * kSnapHashMul) >> (32 - kSnapHashBits);
+    lds_min_u16(tab, h, p - base); // p - base <= 65532 < the 0xffff sentinel
+  }
+  wave_lds_sync();
+}
+
+// Summaries, seam scan and placement of one window; called by all 64 lanes.
+// `carry` and `at` (lane-uniform) are the literals not yet in a sequence and
+// the output offset; both move past this window.
+__device__ __forceinline__ Lz4WavePlan lz4_wave_plan(
+    const uint8_t* __restrict__ in, uint32_t n, uint32_t base, uint32_t wend,
+    const uint16_t* tab, uint32_t lane, uint32_t& carry, uint32_t& at) {
+  Lz4WavePlan pl;
+  uint32_t seg = (uint32_t)snap_segment_size(wend - base); // <= 1024
+  pl.s0 = wend - base > lane * seg ? base + lane * seg : wend;
+  pl.s1 = wend - pl.s0 > seg ? pl.s0 + seg : wend;
+  Lz4Seg none = {0, 0, 0, 0, 0};
+  pl.r = pl.s0 < wend
+             ? lz4_walk_segment<false>(in, n, base, pl.s0, pl.s1, tab, nullptr)
+             : none;
+  // inclusive seam scan, then the element of the lane before
+  Lz4Carry inc = {pl.r.has, pl.r.trail};
+  for (int sh = 1; sh < WAVE; sh <<= 1) {
+    Lz4Carry up = {__shfl_up(inc.has, sh), __shfl_up(inc.trail, sh)};
+    if ((int)lane >= sh) inc = lz4_seam(up, inc);
+  }
+  Lz4Carry ex = {__shfl_up(inc.has, 1), __shfl_up(inc.trail, 1)};
+  if (lane == 0) ex = {0, 0};
+  // the literals of the sequence that this lane's first match closes
+  uint32_t lrun = (ex.has ? ex.trail : carry + ex.trail) + pl.r.lead;
+  pl.hasmask = __ballot(pl.r.has);
+  uint64_t above =
+      lane == WAVE - 1 ? 0 : (pl.hasmask >> (lane + 1)) << (lane + 1);
+  uint32_t nxt = above ? (uint32_t)__builtin_ctzll(above) : lane;
+  pl.later = above != 0;
+  pl.lnext = __shfl(lrun, nxt);
+  pl.nibnext = __shfl(pl.r.nib, nxt);
+  uint32_t bytes = lz4_lane_bytes(pl.r, pl.later, pl.lnext);
+  uint32_t sum = bytes;
+  for (int sh = 1; sh < WAVE; sh <<= 1) {
+    uint32_t v = __shfl_up(sum, sh);
+    if ((int)lane >= sh) sum += v;
+  }
+  uint32_t total = __shfl(sum, WAVE - 1);
+  pl.f0 = pl.hasmask ? (uint32_t)__builtin_ctzll(pl.hasmask) : 0;
+  pl.l0 = __shfl(lrun, pl.f0);
+  pl.nib0 = __shfl(pl.r.nib, pl.f0);
+  uint32_t last_trail = __shfl(inc.trail, WAVE - 1);
+  pl.cin = carry;
+  pl.head_at = at;
+  if (pl.hasmask == 0) { // no sequence ends here: the window is all carry
+    pl.at = at;
+    carry += wend - base;
+    return pl;
+  }
+  uint32_t pre = 1 + lz4_ext_len(pl.l0) + carry;
+  pl.at = at + pre + (sum - bytes);
+  at += pre + total;
+  carry = last_trail;
+  return pl;
+}
+
+// `len` bytes from src to dst by the whole wave, 4 bytes per lane and round
+__device__ __forceinline__ void lz4_wave_copy(uint8_t* dst, const uint8_t* src,
+                                              uint32_t len, uint32_t lane) {
+  uint32_t words = len >> 2;
+  for (uint32_t t = lane; t < words; t += WAVE)
+    store32(dst + 4 * t, load32(src + 4 * t));
+  if (lane < (len & 3u)) dst[4 * words + lane] = src[4 * words + lane];
+}
+
+__device__ __forceinline__ void lz4_wave_emit(const uint8_t* __restrict__ in,
+                                              uint32_t n, uint32_t base,
+                                              uint32_t wend, const uint16_t* tab,
+                                              uint32_t lane,
+                                              const Lz4WavePlan& pl,
+                                              uint8_t* out) {
+  if (pl.hasmask == 0) return;
+  uint32_t head = 1 + lz4_ext_len(pl.l0);
+  if (lane == pl.f0) (void)lz4_put_head(out + pl.head_at, pl.l0, pl.nib0);
+  lz4_wave_copy(out + pl.head_at + head, in + (base - pl.cin), pl.cin, lane);
+  if (pl.s0 < wend)
+    lz4_emit_lane(in, n, base, pl.s0, pl.s1, tab, pl.r, pl.later, pl.lnext,
+                  pl.nibnext, out + pl.at);
+}
+
+__global__ __launch_bounds__(256, 4) void k_compress_lz4(
+    const EmitBlockDesc* __restrict__ bds, uint32_t nblocks,
+    const uint8_t* __restrict__ ucblob, uint8_t* __restrict__ cblob,
+    uint32_t* __restrict__ bsize, uint8_t* __restrict__ btype, uint8_t ctype,
+    uint32_t* err_flag) {
+  __shared__ uint16_t tabs[4][1u << kSnapHashBits]; // 4 KiB per wave
+  uint32_t wid = threadIdx.x / WAVE;
+  uint32_t lane = threadIdx.x % WAVE;
+  uint32_t waves = blockDim.x / WAVE;
+  uint16_t* tab = tabs[wid];
+  for (uint32_t b = blockIdx.x * waves + wid; b < nblocks;
+       b += gridDim.x * waves) {
+    EmitBlockDesc d = bds[b];
+    uint32_t n = d.unc_size;
+    if (n > kLz4MaxUnc) {
+      if (lane == 0) {
+        set_err(err_flag, DE_BLOCK_PARSE);
+        bsize[b] = n;
+        btype[b] = 0;
+      }
+      continue;
+    }
+    const uint8_t* gin = ucblob + d.uout;
+    Lz4WavePlan pl = {};
+    uint32_t carry = 0, at = 0;
+    for (uint32_t base = 0; base < n; base += kLz4Window) {
+      uint32_t wend = n - base > kLz4Window ? base + kLz4Window : n;
+      lz4_wave_table(gin, base, wend, tab, lane);
+      pl = lz4_wave_plan(gin, n, base, wend, tab, lane, carry, at);
+    }
+    uint8_t hdr[5];
+    uint32_t hl = varint32_put(hdr, n); // lane-uniform
+    // the stream ends with the carry as its literal-only sequence
+    uint64_t cn = (uint64_t)hl + at + 1 + lz4_ext_len(carry) + carry;
+    // GoodCompressionRatio before any store, as in k_compress_2p
+    if (cn > (((uint64_t)896 * n) >> 10)) {
+      if (lane == 0) {
+        bsize[b] = n;
+        btype[b] = 0;
+      }
+      continue;
+    }
+    uint8_t* slot = cblob + d.cout;
+    uint8_t* gout = slot + hl; // the raw LZ4 block behind the preamble
+    if (lane == 0) {
+      for (uint32_t t = 0; t < hl; t++) slot[t] = hdr[t];
+      bsize[b] = (uint32_t)cn;
+      btype[b] = ctype;
+    }
+    if (n <= kLz4Window) {
+      lz4_wave_emit(gin, n, 0, n, tab, lane, pl, gout);
+    } else {
+      carry = at = 0;
+      for (uint32_t base = 0; base < n; base += kLz4Window) {
+        uint32_t wend = n - base > kLz4Window ? base + kLz4Window : n;
+        lz4_wave_table(gin, base, wend, tab, lane);
+        pl = lz4_wave_plan(gin, n, base, wend, tab, lane, carry, at);
+        lz4_wave_emit(gin, n, base, wend, tab, lane, pl, gout);
+      }
+    }
+    if (lane == 0) (void)lz4_put_head(gout + at, carry, 0);
+    lz4_wave_copy(gout + at + 1 + lz4_ext_len(carry), gin + (n - carry), carry,
+                  lane);
   }
 }
 

@@ -566,13 +566,22 @@ int check_desc(const dcw_job_desc* d, dcw_job_result* res) {
   if (d->comparator_name &&
       strcmp(d->comparator_name, "leveldb.BytewiseComparator") != 0)
     return fail(res, 12, "unsupported comparator (bytewise only)");
-  if (d->compression > 1)
-    return fail(res, 13, "unsupported compression (none/snappy only)");
+  if (d->compression != 0 && d->compression != 1 && d->compression != 4 &&
+      d->compression != 5)
+    return fail(res, 13,
+                "unsupported output compression (none, snappy, LZ4 or LZ4HC "
+                "only)");
   if (d->checksum_type != 0 && d->checksum_type != 1 && d->checksum_type != 4)
     return fail(res, 14,
                 "unsupported checksum_type (kNoChecksum/kCRC32c/kXXH3 only)");
   if (d->output_table_factory > 1)
     return fail(res, 14, "unsupported output_table_factory");
+  // DcwZipTable value blocks have their own dictionary codec, which a
+  // non-zero compression switches on: LZ4 there would be stored as snappy
+  if (d->output_table_factory == 1 && d->compression > 1)
+    return fail(res, 13,
+                "unsupported: LZ4/LZ4HC output compression with "
+                "output_table_factory = 1 (DcwZipTable)");
   return 0;
 }
 
@@ -920,7 +929,7 @@ int build_bbt_data(JobCtx& c, BbtRun& run, TailJob& f) {
     uint64_t want = d->target_file_size > already
                         ? d->target_file_size - already
                         : (64 << 10);
-    uint64_t min_unc = f.o.compression == 1
+    uint64_t min_unc = f.o.compression != 0
                            ? (uint64_t)(want / run.comp_ratio) +
                                  (uint64_t)(want / run.comp_ratio) / 32 +
                                  16 * f.o.block_size
@@ -943,7 +952,7 @@ int build_bbt_data(JobCtx& c, BbtRun& run, TailJob& f) {
       uint64_t unc_sum = 0, c_sum = 0;
       for (auto& pb : blocks) unc_sum += pb.unc_size;
       for (auto cz : csizes) c_sum += cz;
-      if (f.o.compression == 1 && unc_sum > 0)
+      if (f.o.compression != 0 && unc_sum > 0)
         run.comp_ratio = 0.5 * run.comp_ratio + 0.5 * ((double)c_sum / unc_sum);
     }
     uint64_t old = f.image.len;
