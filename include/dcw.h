@@ -42,9 +42,12 @@ enum {
 enum {
   DCW_COMPRESSION_NONE = 0x0,
   DCW_COMPRESSION_SNAPPY = 0x1,
-  DCW_COMPRESSION_ZSTD = 0x7, /* INPUT blocks only: decoded host-side at
-                                 load (util/compression.h:1332 framing:
-                                 varint32 decompressed size + zstd frame);
+  DCW_COMPRESSION_ZSTD = 0x7, /* INPUT blocks only (util/compression.h:1332
+                                 framing: varint32 decompressed size + zstd
+                                 frame): decoded on the GPU when both sizes
+                                 are within 4992 B and the frame has no
+                                 content checksum, else host-side at load
+                                 (all of them with DCW_ZSTD_HOST=1);
                                  refused as output compression */
   DCW_COMPRESSION_LZ4 = 0x4,  /* input and output, as LZ4HC: varint32 */
   DCW_COMPRESSION_LZ4HC = 0x5, /* decompressed size + one raw LZ4 block

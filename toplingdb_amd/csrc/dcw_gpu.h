@@ -45,6 +45,10 @@ struct GpuInputs {
   // ascending, and their stored bytes: k_decompress_lz4's work list
   std::vector<uint32_t> lz4_blocks;
   uint64_t lz4_stored_bytes = 0;
+  // the same for the zstd blocks (type 7) that zstd_eligible() accepts:
+  // k_decompress_zstd's work list
+  std::vector<uint32_t> zstd_blocks;
+  uint64_t zstd_stored_bytes = 0;
   uint32_t checksum_type = 4;
 };
 
@@ -60,6 +64,8 @@ struct StagedInput {
   std::vector<DztFileRef> dzt_files; // host tables of the DZT files in d_blob
   std::vector<uint32_t> lz4_blocks;  // as GpuInputs
   uint64_t lz4_stored_bytes = 0;
+  std::vector<uint32_t> zstd_blocks; // as GpuInputs
+  uint64_t zstd_stored_bytes = 0;
   ~StagedInput();
 };
 
@@ -226,6 +232,8 @@ class GpuJob {
   std::vector<DztFileRef> dzt_files_; // DZT inputs of the staged job
   std::vector<uint32_t> lz4_blocks_;  // LZ4 blocks of the staged job
   uint64_t lz4_stored_bytes_ = 0;
+  std::vector<uint32_t> zstd_blocks_; // GPU-decoded zstd blocks of the job
+  uint64_t zstd_stored_bytes_ = 0;
   // DZT branch of decode(): table upload, and the key-block decode
   int dzt_upload_tables(std::string* err);
   int dzt_decode_keys(bool general, std::string* err);

@@ -346,6 +346,7 @@ struct GpuJob::Impl {
   DevBuf<uint32_t> d_usize;
   DevBuf<uint8_t> d_btype_in;
   DevBuf<uint32_t> d_lz4idx; // LZ4/LZ4HC input blocks (k_decompress_lz4)
+  DevBuf<uint32_t> d_zstdidx; // zstd input blocks (k_decompress_zstd)
   DevBuf<uint64_t> d_uoff;
   DevBuf<uint8_t> d_ublob;
   uint64_t ublob_size = 0;
@@ -471,6 +472,8 @@ struct GpuJob::Impl {
       if (err) *err = std::string(what) + " failed, code " + std::to_string(e);
       if (err && e == DE_LZ4)
         *err += " (DE_LZ4: bad LZ4/LZ4HC preamble or stream in an input block)";
+      if (err && e == DE_ZSTD)
+        *err += " (DE_ZSTD: bad zstd preamble or frame in an input block)";
       return -1;
     }
     return 0;
@@ -539,6 +542,8 @@ void GpuJob::reset() {
   dzt_files_.clear();
   lz4_blocks_.clear();
   lz4_stored_bytes_ = 0;
+  zstd_blocks_.clear();
+  zstd_stored_bytes_ = 0;
   rd_frags_.clear();
   ms_decode = ms_merge = ms_dedup = ms_emit = ms_h2d = ms_d2h = 0;
 }
@@ -620,6 +625,8 @@ int GpuJob::stage(const GpuInputs& in, std::string* err) {
   dzt_files_ = in.dzt_files;
   lz4_blocks_ = in.lz4_blocks;
   lz4_stored_bytes_ = in.lz4_stored_bytes;
+  zstd_blocks_ = in.zstd_blocks;
+  zstd_stored_bytes_ = in.zstd_stored_bytes;
   return 0;
 }
 
@@ -640,6 +647,8 @@ int GpuJob::stage_adopt(const StagedInput& s, std::string* err) {
   dzt_files_ = s.dzt_files;
   lz4_blocks_ = s.lz4_blocks;
   lz4_stored_bytes_ = s.lz4_stored_bytes;
+  zstd_blocks_ = s.zstd_blocks;
+  zstd_stored_bytes_ = s.zstd_stored_bytes;
   if (p->arm_consts(err) != 0) return -1;
   HIPCHK(hipStreamSynchronize(p->stream));
   return 0;
@@ -659,6 +668,8 @@ int GpuJob::stage_release(StagedInput* s, std::string* err) {
   s->dzt_files = dzt_files_;
   s->lz4_blocks = lz4_blocks_;
   s->lz4_stored_bytes = lz4_stored_bytes_;
+  s->zstd_blocks = zstd_blocks_;
+  s->zstd_stored_bytes = zstd_stored_bytes_;
   return 0;
 }
 
@@ -745,6 +756,21 @@ int GpuJob::decode(std::string* err) {
     hipLaunchKernelGGL(k_decompress_lz4, dim3(grid_for(nl * 64ull)), dim3(256), 0,
                        p->stream, p->d_blob, p->d_boff, p->d_bsize, p->d_uoff,
                        p->d_usize, p->d_lz4idx, nl, p->d_ublob, p->d_err);
+    p->kend();
+  }
+  if (!zstd_blocks_.empty()) {
+    // eligible zstd blocks, which k_decompress skipped: one wave (one
+    // work-group: the decoder's LDS) per listed block
+    uint32_t nl = (uint32_t)zstd_blocks_.size();
+    double decoded = 0;
+    for (uint32_t b : zstd_blocks_) decoded += usize[b];
+    HIPCHK(p->d_zstdidx.reserve(sizeof(uint32_t) * nl));
+    HIPCHK(p->h2d_meta(p->d_zstdidx, zstd_blocks_.data(), sizeof(uint32_t) * nl));
+    p->kbegin("decompress_zstd", (double)zstd_stored_bytes_ + decoded);
+    hipLaunchKernelGGL(k_decompress_zstd, dim3(nl < 8192 ? nl : 8192),
+                       dim3(WAVE), 0, p->stream, p->d_blob, p->d_boff,
+                       p->d_bsize, p->d_uoff, p->d_usize, p->d_zstdidx, nl,
+                       p->d_ublob, p->d_err);
     p->kend();
   }
   if (n_dvb) {

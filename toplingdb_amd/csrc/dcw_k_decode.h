@@ -5,6 +5,8 @@
 #pragma once
 #include "dcw_gpu.h"
 #include "dcw_lz4_dec.h"
+#define DCW_ZSTD_WAVE
+#include "dcw_zstd_dec.h"
 
 #define WAVE 64
 
@@ -21,6 +23,7 @@ enum DevErr : uint32_t {
   DE_COMPRESS_TYPE = 7,
   DE_PLAN_WIDTH = 8,   // planned block exceeds the emit kernel's entry bound
   DE_LZ4 = 9,          // LZ4/LZ4HC input block: bad preamble or stream
+  DE_ZSTD = 10,        // zstd input block: bad preamble or frame
 };
 
 // ------------------------------------------------------------------
@@ -73,6 +76,13 @@ __global__ void k_verify_usize(const uint8_t* __restrict__ blob,
       uint32_t ul;
       if (lz4_preamble(p, sz, &ul) < 0) {
         set_err(err_flag, DE_LZ4);
+        return;
+      }
+      usize[i] = ul;
+    } else if (type == 7) { // zstd (the eligible ones): varint32 preamble
+      uint32_t ul;
+      if (zstd_preamble(p, sz, &ul) < 0) {
+        set_err(err_flag, DE_ZSTD);
         return;
       }
       usize[i] = ul;
@@ -271,7 +281,7 @@ __global__ __launch_bounds__(256) void k_decompress(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
-    } else if (btype[i] != 1) { // type 4 or 5: k_decompress_lz4's block
+    } else if (btype[i] != 1) { // 4, 5: k_decompress_lz4's block; 7: k_decompress_zstd's
     } else if (n <= DEC_MAX && usize[i] <= DEC_MAX) {
       // 16-byte staging: byte-granular copies issued ~5000 DS ops per
       // block per wave and saturated the CU's DS issue pipe that the 16
@@ -344,7 +354,7 @@ __global__ __launch_bounds__(256) void k_decompress_v1(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
-    } else if (btype[i] != 1) { // type 4 or 5: k_decompress_lz4's block
+    } else if (btype[i] != 1) { // 4, 5: k_decompress_lz4's block; 7: k_decompress_zstd's
     } else if (usize[i] <= DEC_MAX) {
       if (lane == 0) {
         if (snappy_uncompress(src, n, L.out, usize[i]) != usize[i])
@@ -391,7 +401,7 @@ __global__ __launch_bounds__(256) void k_decompress_v2(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
-    } else if (btype[i] != 1) { // type 4 or 5: k_decompress_lz4's block
+    } else if (btype[i] != 1) { // 4, 5: k_decompress_lz4's block; 7: k_decompress_zstd's
     } else if (lane == 0) {
       if (snappy_uncompress(src, n, dst, usize[i]) != usize[i])
         set_err(err_flag, DE_SNAPPY);
@@ -455,6 +465,60 @@ __global__ __launch_bounds__(256) void k_decompress_lz4(
     } else if (lane == 0) {
       if (!lz4_dec(src, n, dst, un)) set_err(err_flag, DE_LZ4);
     }
+  }
+}
+
+// zstd input blocks (type 7) that zstd_eligible() accepted, one wave per
+// block over the host-built list of their indices.  One wave is one
+// work-group: the decoder's ZstdWave (frame, decoded block, literals, the
+// Huffman and the three FSE decode tables) is ~33 KiB of LDS.  The frame is
+// staged and the block written back with 16-byte cooperative copies; what the
+// lanes share in between is laid out in dcw_zstd_dec.h.
+static_assert(kZstdMax == DEC_MAX && kZstdPad == DEC_PAD, "one staging size");
+__global__ __launch_bounds__(WAVE) void k_decompress_zstd(
+    const uint8_t* __restrict__ blob, const uint64_t* __restrict__ boff,
+    const uint32_t* __restrict__ bsize, const uint64_t* __restrict__ uoff,
+    const uint32_t* __restrict__ usize, const uint32_t* __restrict__ list,
+    uint32_t nlist, uint8_t* __restrict__ ublob, uint32_t* err_flag) {
+  __shared__ ZstdWave S;
+  const uint32_t lane = threadIdx.x;
+  if (lane < 3) S.tpre[lane] = 0; // no predefined table built yet
+  wave_lds_sync2();
+  for (uint32_t li = blockIdx.x; li < nlist; li += gridDim.x) {
+    uint32_t i = list[li];
+    const uint8_t* src = blob + boff[i];
+    uint8_t* dst = ublob + uoff[i];
+    uint32_t un = usize[i];
+    uint32_t hn = 1; // the preamble again (k_verify_usize accepted it)
+    while (hn < 5 && (src[hn - 1] & 0x80)) hn++;
+    src += hn;
+    uint32_t n = bsize[i] - hn;
+    if (n > DEC_MAX || un > DEC_MAX) { // the host lists eligible blocks only
+      if (lane == 0) set_err(err_flag, DE_ZSTD);
+      continue;
+    }
+    for (uint32_t t = lane * 16; t + 16 <= n; t += WAVE * 16) {
+      ulong2 v;
+      memcpy(&v, src + t, 16);
+      memcpy(S.in + t, &v, 16);
+    }
+    if (lane == 0)
+      for (uint32_t t = n & ~15u; t < n; t++) S.in[t] = src[t];
+    wave_lds_sync2();
+    bool ok = zstd_dec_wave(S, n, un, lane);
+    wave_lds_sync2();
+    if (!ok) {
+      if (lane == 0) set_err(err_flag, DE_ZSTD);
+      continue;
+    }
+    for (uint32_t t = lane * 16; t + 16 <= un; t += WAVE * 16) {
+      ulong2 v;
+      memcpy(&v, S.out + t, 16);
+      memcpy(dst + t, &v, 16);
+    }
+    if (lane == 0)
+      for (uint32_t t = un & ~15u; t < un; t++) dst[t] = S.out[t];
+    wave_lds_sync2();
   }
 }
 

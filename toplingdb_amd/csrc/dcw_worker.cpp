@@ -32,6 +32,7 @@
 #include "../../include/dcw.h"
 #include "dcw_gpu.h"
 #include "dcw_host.h"
+#include "dcw_zstd_dec.h"
 
 namespace dcw {
 namespace {
@@ -266,16 +267,16 @@ struct LoadedInputs {
   GpuInputs gi;
   uint64_t in_bytes = 0;
   std::vector<SstTombstone> tombstones; // all inputs' range deletions
-  bool host_decoded = false; // zstd inputs were rewritten (see below)
+  bool host_decoded = false; // host-only zstd inputs were rewritten (below)
   // sub-phase wall attribution (printed under DCW_PHASE_DEBUG)
   uint64_t us_reserve = 0, us_pread = 0, us_parse = 0, us_stage = 0;
   uint64_t us_dzt_keycsum = 0; // part of us_parse: DZT key-area checksums
 };
 
 // minimal libzstd ABI (runtime lib only in this image); the worker only
-// DECODES zstd inputs — SURVEY §8f-1's input side.  The GPU codec stays
-// snappy; zstd blocks are decoded host-side at load and handed to the
-// device as raw blocks with recomputed trailers.
+// DECODES zstd inputs — SURVEY §8f-1's input side.  Blocks that
+// k_decompress_zstd does not take are decoded host-side at load and handed
+// to the device as raw blocks with recomputed trailers.
 extern "C" size_t ZSTD_decompress(void*, size_t, const void*, size_t);
 extern "C" unsigned ZSTD_isError(size_t);
 
@@ -426,22 +427,35 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
     }
     L->gi.run_block_begin.push_back((uint32_t)L->gi.blocks.size());
   }
-  // zstd input blocks (type byte 0x7 in the trailer): verify + decode on
-  // the host, rebuild the staged blob with raw blocks + recomputed
-  // trailers (decompression output is unique, so parity is unaffected;
-  // the reference reads its inputs through the same libzstd,
-  // util/compression.h ZSTD_Uncompress)
-  bool any_zstd = false;
+  // zstd input blocks (type byte 0x7 in the trailer).  The ones the
+  // eligibility walk accepts (dcw_zstd_dec.h: one plain frame within the
+  // decoder's staging size) stay as they are and are listed for
+  // k_decompress_zstd.  The rest (larger blocks, frames with a content
+  // checksum, anything the walk does not like) are HOST-ONLY: verified and
+  // decoded here with libzstd and the staged blob rebuilt with them as raw
+  // blocks + recomputed trailers (decompression output is unique, so parity
+  // is unaffected; the reference reads its inputs through the same libzstd,
+  // util/compression.h ZSTD_Uncompress).  DCW_ZSTD_HOST=1, read per job,
+  // makes every zstd block host-only.
+  bool any_zstd = false, any_host_zstd = false;
   uint32_t ct = cstype == 0xffffffff ? 4 : cstype;
   tphase = now_usec();
+  const char* zh = getenv("DCW_ZSTD_HOST");
+  const bool zstd_on_host = zh && atoi(zh) != 0;
   // the same walk lists the LZ4 / LZ4HC blocks (types 4 and 5) for
-  // k_decompress_lz4; the rewrite below keeps block order and copies
-  // non-zstd blocks verbatim, so the indices hold either way
+  // k_decompress_lz4; the rewrite below keeps block order and copies every
+  // block that is not host-only verbatim, so the indices hold either way
   for (size_t bi = 0; bi < L->gi.blocks.size(); bi++) {
     const BlockRef& blk = L->gi.blocks[bi];
     uint8_t type = L->blob.p[blk.off + blk.size];
     if (type == 7) {
       any_zstd = true;
+      if (!zstd_on_host && zstd_eligible(L->blob.p + blk.off, blk.size)) {
+        L->gi.zstd_blocks.push_back((uint32_t)bi);
+        L->gi.zstd_stored_bytes += blk.size;
+      } else {
+        any_host_zstd = true;
+      }
     } else if (type == 4 || type == 5) {
       L->gi.lz4_blocks.push_back((uint32_t)bi);
       L->gi.lz4_stored_bytes += blk.size;
@@ -453,18 +467,22 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
     *err = "zstd BlockBasedTable inputs cannot be combined with DZT inputs";
     return -1;
   }
-  if (any_zstd) {
+  if (any_host_zstd) {
     if (job) { // already-streamed chunks are superseded by a full restage
       job->stage_cancel();
     }
     RawBuf nb;
     uint64_t est = L->blob.len * 2 + (16u << 20);
     nb.reserve(est);
-    for (auto& blk : L->gi.blocks) {
+    size_t zi = 0; // next GPU-decoded zstd block, in block order
+    for (size_t bi = 0; bi < L->gi.blocks.size(); bi++) {
+      BlockRef& blk = L->gi.blocks[bi];
       const uint8_t* body = L->blob.p + blk.off;
       uint8_t type = body[blk.size];
       uint64_t noff = nb.len;
-      if (type == 7) {
+      bool on_gpu = zi < L->gi.zstd_blocks.size() && L->gi.zstd_blocks[zi] == bi;
+      zi += on_gpu;
+      if (type == 7 && !on_gpu) {
         uint32_t stored;
         memcpy(&stored, body + blk.size + 1, 4);
         if (ct != 0 &&
