@@ -44,10 +44,12 @@ enum {
   DCW_COMPRESSION_SNAPPY = 0x1,
   DCW_COMPRESSION_ZSTD = 0x7, /* INPUT blocks only (util/compression.h:1332
                                  framing: varint32 decompressed size + zstd
-                                 frame): decoded on the GPU when both sizes
-                                 are within 4992 B and the frame has no
-                                 content checksum, else host-side at load
-                                 (all of them with DCW_ZSTD_HOST=1);
+                                 frame): decoded on the GPU when the frame
+                                 has no content checksum (by a second
+                                 kernel when a size is over 4992 B), else
+                                 host-side at load (all of them with
+                                 DCW_ZSTD_HOST=1, the ones over 4992 B with
+                                 DCW_ZSTD_LARGE_HOST=1);
                                  refused as output compression */
   DCW_COMPRESSION_LZ4 = 0x4,  /* input and output, as LZ4HC: varint32 */
   DCW_COMPRESSION_LZ4HC = 0x5, /* decompressed size + one raw LZ4 block

@@ -49,6 +49,10 @@ struct GpuInputs {
   // k_decompress_zstd's work list
   std::vector<uint32_t> zstd_blocks;
   uint64_t zstd_stored_bytes = 0;
+  // and for the larger ones that zstd_eligible_large() accepts:
+  // k_decompress_zstd_large's work list
+  std::vector<uint32_t> zstd_large_blocks;
+  uint64_t zstd_large_stored_bytes = 0;
   uint32_t checksum_type = 4;
 };
 
@@ -66,6 +70,8 @@ struct StagedInput {
   uint64_t lz4_stored_bytes = 0;
   std::vector<uint32_t> zstd_blocks; // as GpuInputs
   uint64_t zstd_stored_bytes = 0;
+  std::vector<uint32_t> zstd_large_blocks; // as GpuInputs
+  uint64_t zstd_large_stored_bytes = 0;
   ~StagedInput();
 };
 
@@ -234,6 +240,8 @@ class GpuJob {
   uint64_t lz4_stored_bytes_ = 0;
   std::vector<uint32_t> zstd_blocks_; // GPU-decoded zstd blocks of the job
   uint64_t zstd_stored_bytes_ = 0;
+  std::vector<uint32_t> zstd_large_blocks_; // k_decompress_zstd_large's
+  uint64_t zstd_large_stored_bytes_ = 0;
   // DZT branch of decode(): table upload, and the key-block decode
   int dzt_upload_tables(std::string* err);
   int dzt_decode_keys(bool general, std::string* err);

@@ -347,6 +347,8 @@ struct GpuJob::Impl {
   DevBuf<uint8_t> d_btype_in;
   DevBuf<uint32_t> d_lz4idx; // LZ4/LZ4HC input blocks (k_decompress_lz4)
   DevBuf<uint32_t> d_zstdidx; // zstd input blocks (k_decompress_zstd)
+  DevBuf<uint32_t> d_zstdlidx; // the large ones (k_decompress_zstd_large)
+  DevBuf<uint8_t> d_zstdlit;   // its literal scratch, kZLitStride per work-group
   DevBuf<uint64_t> d_uoff;
   DevBuf<uint8_t> d_ublob;
   uint64_t ublob_size = 0;
@@ -544,6 +546,8 @@ void GpuJob::reset() {
   lz4_stored_bytes_ = 0;
   zstd_blocks_.clear();
   zstd_stored_bytes_ = 0;
+  zstd_large_blocks_.clear();
+  zstd_large_stored_bytes_ = 0;
   rd_frags_.clear();
   ms_decode = ms_merge = ms_dedup = ms_emit = ms_h2d = ms_d2h = 0;
 }
@@ -627,6 +631,8 @@ int GpuJob::stage(const GpuInputs& in, std::string* err) {
   lz4_stored_bytes_ = in.lz4_stored_bytes;
   zstd_blocks_ = in.zstd_blocks;
   zstd_stored_bytes_ = in.zstd_stored_bytes;
+  zstd_large_blocks_ = in.zstd_large_blocks;
+  zstd_large_stored_bytes_ = in.zstd_large_stored_bytes;
   return 0;
 }
 
@@ -649,6 +655,8 @@ int GpuJob::stage_adopt(const StagedInput& s, std::string* err) {
   lz4_stored_bytes_ = s.lz4_stored_bytes;
   zstd_blocks_ = s.zstd_blocks;
   zstd_stored_bytes_ = s.zstd_stored_bytes;
+  zstd_large_blocks_ = s.zstd_large_blocks;
+  zstd_large_stored_bytes_ = s.zstd_large_stored_bytes;
   if (p->arm_consts(err) != 0) return -1;
   HIPCHK(hipStreamSynchronize(p->stream));
   return 0;
@@ -670,6 +678,8 @@ int GpuJob::stage_release(StagedInput* s, std::string* err) {
   s->lz4_stored_bytes = lz4_stored_bytes_;
   s->zstd_blocks = zstd_blocks_;
   s->zstd_stored_bytes = zstd_stored_bytes_;
+  s->zstd_large_blocks = zstd_large_blocks_;
+  s->zstd_large_stored_bytes = zstd_large_stored_bytes_;
   return 0;
 }
 
@@ -771,6 +781,27 @@ int GpuJob::decode(std::string* err) {
                        dim3(WAVE), 0, p->stream, p->d_blob, p->d_boff,
                        p->d_bsize, p->d_uoff, p->d_usize, p->d_zstdidx, nl,
                        p->d_ublob, p->d_err);
+    p->kend();
+  }
+  if (!zstd_large_blocks_.empty()) {
+    // zstd blocks beyond the small decoder's staging: one wave (one
+    // work-group) per listed block, global to global.  The grid is capped at
+    // what 256 compute units hold at 8 work-groups each, and each work-group
+    // of the grid owns kZLitStride bytes of literal scratch (256 MiB at the
+    // cap).
+    uint32_t nl = (uint32_t)zstd_large_blocks_.size();
+    uint32_t grid = nl < 2048 ? nl : 2048;
+    double decoded = 0;
+    for (uint32_t b : zstd_large_blocks_) decoded += usize[b];
+    HIPCHK(p->d_zstdlidx.reserve(sizeof(uint32_t) * nl));
+    HIPCHK(p->h2d_meta(p->d_zstdlidx, zstd_large_blocks_.data(),
+                       sizeof(uint32_t) * nl));
+    HIPCHK(p->d_zstdlit.reserve((size_t)grid * kZLitStride));
+    p->kbegin("decompress_zstd_large", (double)zstd_large_stored_bytes_ + decoded);
+    launch_decompress_zstd_large(grid, p->stream, p->d_blob, p->d_boff,
+                                 p->d_bsize, p->d_uoff, p->d_usize,
+                                 p->d_zstdlidx, nl, p->d_ublob, p->d_zstdlit,
+                                 p->d_err, DE_ZSTD);
     p->kend();
   }
   if (n_dvb) {

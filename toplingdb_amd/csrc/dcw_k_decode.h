@@ -7,6 +7,7 @@
 #include "dcw_lz4_dec.h"
 #define DCW_ZSTD_WAVE
 #include "dcw_zstd_dec.h"
+#include "dcw_zstd_dec_large.h" // kZLitStride and the launcher of dcw_zstd_large.hip
 
 #define WAVE 64
 

@@ -33,6 +33,7 @@
 #include "dcw_gpu.h"
 #include "dcw_host.h"
 #include "dcw_zstd_dec.h"
+#include "dcw_zstd_dec_large.h"
 
 namespace dcw {
 namespace {
@@ -430,18 +431,24 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
   // zstd input blocks (type byte 0x7 in the trailer).  The ones the
   // eligibility walk accepts (dcw_zstd_dec.h: one plain frame within the
   // decoder's staging size) stay as they are and are listed for
-  // k_decompress_zstd.  The rest (larger blocks, frames with a content
-  // checksum, anything the walk does not like) are HOST-ONLY: verified and
+  // k_decompress_zstd; larger ones that the second walk accepts
+  // (dcw_zstd_dec_large.h) are listed for k_decompress_zstd_large.  The rest
+  // (frames with a content checksum, anything the walks do not like) are
+  // HOST-ONLY: verified and
   // decoded here with libzstd and the staged blob rebuilt with them as raw
   // blocks + recomputed trailers (decompression output is unique, so parity
   // is unaffected; the reference reads its inputs through the same libzstd,
   // util/compression.h ZSTD_Uncompress).  DCW_ZSTD_HOST=1, read per job,
-  // makes every zstd block host-only.
+  // makes every zstd block host-only, DCW_ZSTD_LARGE_HOST=1 only the ones
+  // the small kernel does not take.  A job without host-only blocks skips the
+  // rebuild.
   bool any_zstd = false, any_host_zstd = false;
   uint32_t ct = cstype == 0xffffffff ? 4 : cstype;
   tphase = now_usec();
   const char* zh = getenv("DCW_ZSTD_HOST");
   const bool zstd_on_host = zh && atoi(zh) != 0;
+  const char* zlh = getenv("DCW_ZSTD_LARGE_HOST");
+  const bool zstd_large_on_host = zstd_on_host || (zlh && atoi(zlh) != 0);
   // the same walk lists the LZ4 / LZ4HC blocks (types 4 and 5) for
   // k_decompress_lz4; the rewrite below keeps block order and copies every
   // block that is not host-only verbatim, so the indices hold either way
@@ -453,6 +460,10 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
       if (!zstd_on_host && zstd_eligible(L->blob.p + blk.off, blk.size)) {
         L->gi.zstd_blocks.push_back((uint32_t)bi);
         L->gi.zstd_stored_bytes += blk.size;
+      } else if (!zstd_large_on_host &&
+                 zstd_eligible_large(L->blob.p + blk.off, blk.size)) {
+        L->gi.zstd_large_blocks.push_back((uint32_t)bi);
+        L->gi.zstd_large_stored_bytes += blk.size;
       } else {
         any_host_zstd = true;
       }
@@ -474,7 +485,7 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
     RawBuf nb;
     uint64_t est = L->blob.len * 2 + (16u << 20);
     nb.reserve(est);
-    size_t zi = 0; // next GPU-decoded zstd block, in block order
+    size_t zi = 0, zli = 0; // next GPU-decoded zstd block of either list
     for (size_t bi = 0; bi < L->gi.blocks.size(); bi++) {
       BlockRef& blk = L->gi.blocks[bi];
       const uint8_t* body = L->blob.p + blk.off;
@@ -482,6 +493,10 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
       uint64_t noff = nb.len;
       bool on_gpu = zi < L->gi.zstd_blocks.size() && L->gi.zstd_blocks[zi] == bi;
       zi += on_gpu;
+      if (zli < L->gi.zstd_large_blocks.size() && L->gi.zstd_large_blocks[zli] == bi) {
+        on_gpu = true;
+        zli++;
+      }
       if (type == 7 && !on_gpu) {
         uint32_t stored;
         memcpy(&stored, body + blk.size + 1, 4);

@@ -49,6 +49,7 @@ namespace dcw {
 static const uint32_t kZstdMax = 4992; // == DEC_MAX (dcw_k_decode.h)
 static const uint32_t kZstdPad = 16;   // slack for the 8-byte bit fetches
 static const uint32_t kZstdMagic = 0xFD2FB528u;
+static const uint32_t kZstdBlockMax = 128u << 10; // Block_Maximum_Size
 
 ZHD int zstd_preamble(const uint8_t* p, uint32_t n, uint32_t* usize) {
   uint32_t r = 0;
@@ -157,6 +158,21 @@ struct alignas(16) ZstdWave {
   int32_t sq_pos;
 };
 
+// Where the frame, the decoded bytes and the literals live is a memory
+// policy M beside the state ZS; the format code below is shared.  ZMemLds:
+// all three are arrays of the ZstdWave.  (dcw_zstd_dec_large.h has the
+// policy that keeps them in global memory.)  A policy comes with
+//   zm_in(S, m)            the frame
+//   zm_wscr(S)             1536 bytes of scratch for the Huffman table build
+//   zm_huf_literals        the 1 or 4 Huffman streams -> literals
+//   zm_rle_literals        RLE literals
+//   zm_exec_batch          literal runs and matches of a placed batch
+//   zm_tail_literals       the literals behind the last sequence
+//   zm_plain_block         a raw or RLE block
+struct ZMemLds {};
+ZFN const uint8_t* zm_in(const ZstdWave& S, const ZMemLds&) { return S.in; }
+ZFN uint8_t* zm_wscr(ZstdWave& S) { return S.lit; }
+
 ZFN uint32_t z_highbit(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
 ZFN uint64_t z_ld64(const uint8_t* p) {
   uint32_t lo, hi;
@@ -166,7 +182,8 @@ ZFN uint64_t z_ld64(const uint8_t* p) {
 }
 
 // exclusive prefix sums of scan[0..64), in place
-ZFN void zw_scan(ZstdWave& S, uint32_t zlane) {
+template <class ZS>
+ZFN void zw_scan(ZS& S, uint32_t zlane) {
 #if defined(__HIPCC__)
   ZW_SYNC();
   unsigned long long v = S.scan[zlane], inc = v;
@@ -264,7 +281,8 @@ ZFN uint32_t zf_peek(const uint8_t* p, uint32_t n, uint32_t bit, uint32_t nb) {
     if (byte + k < n) v |= (uint32_t)p[byte + k] << (8 * k);
   return (v >> (bit & 7)) & ((1u << nb) - 1);
 }
-ZFN uint32_t zstd_read_ncount(ZstdWave& S, const uint8_t* p, uint32_t n,
+template <class ZS>
+ZFN uint32_t zstd_read_ncount(ZS& S, const uint8_t* p, uint32_t n,
                               uint32_t max_sym, uint32_t max_log) {
   if (n == 0) return 0;
   uint32_t log = zf_peek(p, n, 0, 4) + 5, bit = 4;
@@ -311,7 +329,8 @@ ZFN uint32_t zstd_read_ncount(ZstdWave& S, const uint8_t* p, uint32_t n,
 }
 
 // ---- FSE decode table from norm[0..nsym) and blog, by the whole wave
-ZFN void zstd_fse_build(ZstdWave& S, uint64_t* T, uint32_t kind, uint32_t zlane) {
+template <class ZS>
+ZFN void zstd_fse_build(ZS& S, uint64_t* T, uint32_t kind, uint32_t zlane) {
   const uint32_t log = S.blog, size = 1u << log, mask = size - 1;
   const uint32_t step = (size >> 1) + (size >> 3) + 3, nsym = S.nsym;
   const uint32_t per = (size + 63) >> 6;
@@ -369,8 +388,9 @@ ZFN void zstd_fse_build(ZstdWave& S, uint64_t* T, uint32_t kind, uint32_t zlane)
 }
 
 // ---- Huffman: weights -> rank layout (lane 0), then the table (wave)
-ZFN void zstd_huf_weights_done(ZstdWave& S, uint32_t nw) {
-  uint8_t* W = S.lit;
+template <class ZS>
+ZFN void zstd_huf_weights_done(ZS& S, uint32_t nw) {
+  uint8_t* W = zm_wscr(S);
   uint32_t total = 0;
   for (uint32_t w = 0; w < 12; w++) S.rank[w] = 0;
   for (uint32_t i = 0; i < nw; i++) {
@@ -398,12 +418,13 @@ ZFN void zstd_huf_weights_done(ZstdWave& S, uint32_t nw) {
   S.hnsym = nw + 1;
   S.hnz = k;
 }
-ZFN void zstd_huf_build(ZstdWave& S, uint32_t zlane) {
+template <class ZS>
+ZFN void zstd_huf_build(ZS& S, uint32_t zlane) {
   (void)zlane;
   const uint32_t log = S.hlog, nsym = S.hnsym, nz = S.hnz, size = 1u << log;
-  const uint8_t* W = S.lit;
-  uint16_t* sstart = (uint16_t*)(S.lit + 512);  // by table position:
-  uint16_t* sval = (uint16_t*)(S.lit + 1024);   // first cell, cell value
+  const uint8_t* W = zm_wscr(S);
+  uint16_t* sstart = (uint16_t*)(zm_wscr(S) + 512);  // by table position:
+  uint16_t* sval = (uint16_t*)(zm_wscr(S) + 1024);   // first cell, cell value
   ZW_LANES { // one lane per weight: its symbols in order, lowest cells first
     if (lane < 1 || lane > log) continue;
     uint32_t k = S.sbase[lane], cur = S.rstart[lane];
@@ -446,10 +467,11 @@ ZFN void zstd_huf_stream(ZstdWave& S, uint32_t k) {
   if (b.pos != 0) S.fail = 1;
 }
 // the Huffman weights' own FSE stream: two interleaved states (lane 0)
-ZFN void zstd_huf_fse_weights(ZstdWave& S) {
+template <class ZS>
+ZFN void zstd_huf_fse_weights(ZS& S, const uint8_t* in) {
   ZBack b;
-  if (!zb_init(b, S.in + S.ws_start, S.ws_len)) { S.fail = 1; return; }
-  uint8_t* W = S.lit;
+  if (!zb_init(b, in + S.ws_start, S.ws_len)) { S.fail = 1; return; }
+  uint8_t* W = zm_wscr(S);
   uint32_t s1 = zb_read(b, S.blog), s2 = zb_read(b, S.blog), n = 0;
   if (b.pos < 0) { S.fail = 1; return; }
   for (;;) {
@@ -467,14 +489,15 @@ ZFN void zstd_huf_fse_weights(ZstdWave& S) {
   zstd_huf_weights_done(S, n);
 }
 // where the 1 or 4 streams lie (lane 0); region = [hs_rs, +hs_rl)
-ZFN void zstd_lit_streams(ZstdWave& S) {
+template <class ZS>
+ZFN void zstd_lit_streams(ZS& S, const uint8_t* in) {
   uint32_t rs = S.hs_rs, rl = S.hs_rl, ls = S.lit_size;
   if (S.nstreams == 1) {
     S.hs_start[0] = rs; S.hs_len[0] = rl; S.hs_out[0] = 0; S.hs_cnt[0] = ls;
     return;
   }
   if (rl < 10) { S.fail = 1; return; }
-  const uint8_t* p = S.in + rs;
+  const uint8_t* p = in + rs;
   uint32_t l1 = p[0] | (p[1] << 8), l2 = p[2] | (p[3] << 8), l3 = p[4] | (p[5] << 8);
   uint32_t seg = (ls + 3) >> 2;
   if (6 + l1 + l2 + l3 > rl || 3 * seg > ls) { S.fail = 1; return; }
@@ -488,11 +511,12 @@ ZFN void zstd_lit_streams(ZstdWave& S) {
 }
 
 // ---- headers (lane 0)
-ZFN void zstd_frame_header(ZstdWave& S, uint32_t n, uint32_t cap) {
+template <class ZS>
+ZFN void zstd_frame_header(ZS& S, const uint8_t* in, uint32_t n, uint32_t cap) {
   S.fail = 0; S.op = 0; S.last = 0;
   S.have_huf = S.have_fse = 0;
   S.rep1 = 1; S.rep2 = 4; S.rep3 = 8;
-  const uint8_t* p = S.in;
+  const uint8_t* p = in;
   if (n < 6) { S.fail = 1; return; }
   uint32_t magic;
   memcpy(&magic, p, 4);
@@ -514,23 +538,27 @@ ZFN void zstd_frame_header(ZstdWave& S, uint32_t n, uint32_t cap) {
   }
   S.ip = ip + fb;
 }
-ZFN void zstd_block_header(ZstdWave& S, uint32_t n, uint32_t cap) {
+template <class ZS>
+ZFN void zstd_block_header(ZS& S, const uint8_t* in, uint32_t n, uint32_t cap) {
   uint32_t ip = S.ip;
   if (ip + 3 > n) { S.fail = 1; return; }
-  const uint8_t* p = S.in + ip;
+  const uint8_t* p = in + ip;
   uint32_t h = p[0] | (p[1] << 8) | ((uint32_t)p[2] << 16);
   uint32_t type = (h >> 1) & 3, sz = h >> 3;
   ip += 3;
   S.last = h & 1; S.btype = type; S.bsize = sz;
   uint32_t stored = type == 1 ? 1 : sz;
+  // a compressed block of Block_Maximum_Size is refused as by libzstd
   if (type == 3 || stored > n - ip || (type == 2 && sz < 3) ||
-      (type != 2 && sz > cap - S.op)) { S.fail = 1; return; }
+      (type != 2 && sz > cap - S.op) || sz > kZstdBlockMax ||
+      (type == 2 && sz == kZstdBlockMax)) { S.fail = 1; return; }
   S.ip = ip;
   S.bend = ip + stored;
 }
-ZFN void zstd_lit_header(ZstdWave& S, uint32_t cap) {
+template <class ZS>
+ZFN void zstd_lit_header(ZS& S, const uint8_t* in, uint32_t cap) {
   const uint32_t bs = S.ip, bsz = S.bend - bs; // bsz >= 3
-  const uint8_t* p = S.in + bs;
+  const uint8_t* p = in + bs;
   uint32_t type = p[0] & 3, sf = (p[0] >> 2) & 3, lh, ls, cs = 0;
   S.lit_inplace = S.lit_fill = S.need_wfse = 0;
   S.lit_tree = type == 2;
@@ -540,7 +568,10 @@ ZFN void zstd_lit_header(ZstdWave& S, uint32_t cap) {
     if (!(sf & 1)) { lh = 1; ls = p[0] >> 3; }
     else if (sf == 1) { lh = 2; ls = (p[0] | (p[1] << 8)) >> 4; }
     else { lh = 3; ls = (p[0] | (p[1] << 8) | ((uint32_t)p[2] << 16)) >> 4; }
-    if (ls > cap - S.op || lh + (type == 0 ? ls : 1) > bsz) { S.fail = 1; return; }
+    if (ls > cap - S.op || ls > kZstdBlockMax || lh + (type == 0 ? ls : 1) > bsz) {
+      S.fail = 1;
+      return;
+    }
     S.lit_size = ls;
     if (type == 0) {
       ZSTAT(ZS_LIT_RAW);
@@ -561,7 +592,7 @@ ZFN void zstd_lit_header(ZstdWave& S, uint32_t cap) {
   else if (sf == 2) { lh = 4; ls = (lhc >> 4) & 0x3fff; cs = lhc >> 18; }
   else { lh = 5; ls = (lhc >> 4) & 0x3ffff; cs = (lhc >> 22) + ((uint32_t)p[4] << 10); }
   S.nstreams = sf == 0 ? 1 : 4;
-  if (ls == 0 || cs == 0 || ls > cap - S.op || lh + cs > bsz ||
+  if (ls == 0 || cs == 0 || ls > cap - S.op || ls > kZstdBlockMax || lh + cs > bsz ||
       (type == 3 && !S.have_huf)) { S.fail = 1; return; }
   S.lit_size = ls;
   S.ip = bs + lh + cs;
@@ -570,19 +601,19 @@ ZFN void zstd_lit_header(ZstdWave& S, uint32_t cap) {
   if (type == 3) {
     ZSTAT(ZS_LIT_TREELESS);
     S.hs_rs = at; S.hs_rl = cs;
-    zstd_lit_streams(S);
+    zstd_lit_streams(S, in);
     return;
   }
   S.have_huf = 1;
-  uint32_t hb = S.in[at], desc;
-  uint8_t* W = S.lit;
+  uint32_t hb = in[at], desc;
+  uint8_t* W = zm_wscr(S);
   if (hb >= 128) { // direct 4-bit weights
     ZSTAT(ZS_W_DIRECT);
     uint32_t nw = hb - 127;
     desc = 1 + ((nw + 1) >> 1);
     if (desc >= cs) { S.fail = 1; return; }
     for (uint32_t i = 0; i < nw; i++) {
-      uint32_t b = S.in[at + 1 + (i >> 1)];
+      uint32_t b = in[at + 1 + (i >> 1)];
       W[i] = (uint8_t)((i & 1) ? (b & 15) : (b >> 4));
     }
     zstd_huf_weights_done(S, nw);
@@ -590,20 +621,21 @@ ZFN void zstd_lit_header(ZstdWave& S, uint32_t cap) {
     ZSTAT(ZS_W_FSE);
     desc = 1 + hb;
     if (hb == 0 || desc >= cs) { S.fail = 1; return; }
-    uint32_t c = zstd_read_ncount(S, S.in + at + 1, hb, 11, 6);
+    uint32_t c = zstd_read_ncount(S, in + at + 1, hb, 11, 6);
     if (c == 0 || c >= hb) { S.fail = 1; return; }
     S.need_wfse = 1;
     S.ws_start = at + 1 + c;
     S.ws_len = hb - c;
   }
   S.hs_rs = at + desc; S.hs_rl = cs - desc;
-  if (!S.fail) zstd_lit_streams(S);
+  if (!S.fail) zstd_lit_streams(S, in);
 }
-ZFN void zstd_seq_header(ZstdWave& S) {
+template <class ZS>
+ZFN void zstd_seq_header(ZS& S, const uint8_t* in) {
   uint32_t ip = S.ip, bend = S.bend;
   S.nseq = 0;
   if (ip >= bend) { S.fail = 1; return; }
-  uint32_t b0 = S.in[ip++], nseq;
+  uint32_t b0 = in[ip++], nseq;
   if (b0 == 0) {
     ZSTAT(ZS_NSEQ_0);
     if (ip != bend) S.fail = 1;
@@ -612,23 +644,24 @@ ZFN void zstd_seq_header(ZstdWave& S) {
   if (b0 < 128) { nseq = b0; ZSTAT(ZS_NSEQ_1B); }
   else if (b0 < 255) {
     if (ip >= bend) { S.fail = 1; return; }
-    nseq = ((b0 - 128) << 8) + S.in[ip++];
+    nseq = ((b0 - 128) << 8) + in[ip++];
     if (nseq == 0) { S.fail = 1; return; }
     ZSTAT(ZS_NSEQ_2B);
   } else {
     if (ip + 2 > bend) { S.fail = 1; return; }
-    nseq = (S.in[ip] | (S.in[ip + 1] << 8)) + 0x7f00;
+    nseq = (in[ip] | (in[ip + 1] << 8)) + 0x7f00;
     ip += 2;
     ZSTAT(ZS_NSEQ_3B);
   }
   if (ip >= bend) { S.fail = 1; return; }
-  S.modes = S.in[ip++];
+  S.modes = in[ip++];
   if (S.modes & 3) { S.fail = 1; return; }
   S.nseq = nseq;
   S.ip = ip;
 }
 // table t of the block (0 LL, 1 OF, 2 ML): read its mode's description
-ZFN void zstd_seq_table(ZstdWave& S, uint32_t t) {
+template <class ZS>
+ZFN void zstd_seq_table(ZS& S, const uint8_t* in, uint32_t t) {
   const uint32_t mode = (S.modes >> (6 - 2 * t)) & 3;
   const uint32_t max_sym = t == ZT_LL ? 35 : t == ZT_OF ? 31 : 52;
   uint64_t* T = t == ZT_LL ? S.tLL : t == ZT_OF ? S.tOF : S.tML;
@@ -643,13 +676,13 @@ ZFN void zstd_seq_table(ZstdWave& S, uint32_t t) {
     S.tpre[t] = 1;
   } else if (mode == 1) {
     ZSTAT(ZS_LL_RLE + 4 * t);
-    if (S.ip >= S.bend || S.in[S.ip] > max_sym) { S.fail = 1; return; }
-    T[0] = z_cell(t, S.in[S.ip++], 0, 0);
+    if (S.ip >= S.bend || in[S.ip] > max_sym) { S.fail = 1; return; }
+    T[0] = z_cell(t, in[S.ip++], 0, 0);
     S.tlog[t] = 0;
     S.tpre[t] = 0;
   } else if (mode == 2) {
     ZSTAT(ZS_LL_FSE + 4 * t);
-    uint32_t c = zstd_read_ncount(S, S.in + S.ip, S.bend - S.ip, max_sym,
+    uint32_t c = zstd_read_ncount(S, in + S.ip, S.bend - S.ip, max_sym,
                                   t == ZT_OF ? 8 : 9);
     if (c == 0) { S.fail = 1; return; }
     S.ip += c;
@@ -661,9 +694,10 @@ ZFN void zstd_seq_table(ZstdWave& S, uint32_t t) {
   }
   if (S.build) S.tlog[t] = S.blog;
 }
-ZFN void zstd_seq_init(ZstdWave& S) {
+template <class ZS>
+ZFN void zstd_seq_init(ZS& S, const uint8_t* in) {
   ZBack b;
-  if (!zb_init(b, S.in + S.ip, S.bend - S.ip)) { S.fail = 1; return; }
+  if (!zb_init(b, in + S.ip, S.bend - S.ip)) { S.fail = 1; return; }
   S.stLL = zb_read(b, S.tlog[ZT_LL]);
   S.stOF = zb_read(b, S.tlog[ZT_OF]);
   S.stML = zb_read(b, S.tlog[ZT_ML]);
@@ -673,8 +707,9 @@ ZFN void zstd_seq_init(ZstdWave& S) {
   S.have_fse = 1;
 }
 // lane 0: the next cnt (<= 64) sequences into seq_ll/seq_ml/seq_off
-ZFN void zstd_seq_batch(ZstdWave& S, uint32_t cnt, bool final_batch) {
-  ZBack b = {S.in + S.sq_start, S.sq_pos};
+template <class ZS>
+ZFN void zstd_seq_batch(ZS& S, const uint8_t* in, uint32_t cnt, bool final_batch) {
+  ZBack b = {in + S.sq_start, S.sq_pos};
   uint32_t sl = S.stLL, so = S.stOF, sm = S.stML;
   uint32_t r1 = S.rep1, r2 = S.rep2, r3 = S.rep3;
   for (uint32_t k = 0; k < cnt; k++) {
@@ -712,49 +747,105 @@ ZFN void zstd_seq_batch(ZstdWave& S, uint32_t cnt, bool final_batch) {
   S.rep1 = r1; S.rep2 = r2; S.rep3 = r3;
 }
 
+// ---- ZMemLds: the moves of a block inside the ZstdWave
+ZFN bool zm_huf_literals(ZstdWave& S, const ZMemLds&, uint32_t zlane) {
+  (void)zlane;
+  const uint32_t ns = S.nstreams;
+  ZW_LANES { if (lane < ns) zstd_huf_stream(S, lane); }
+  ZW_SYNC();
+  return !S.fail;
+}
+ZFN void zm_rle_literals(ZstdWave& S, const ZMemLds&, uint32_t zlane) {
+  (void)zlane;
+  const uint32_t ls = S.lit_size, v = S.lit_rle;
+  ZW_LANES { for (uint32_t i = lane; i < ls; i += 64) S.lit[i] = (uint8_t)v; }
+  ZW_SYNC();
+}
+ZFN void zm_exec_batch(ZstdWave& S, const ZMemLds&, uint32_t cnt, uint32_t zlane) {
+  (void)zlane;
+  const uint8_t* lit = S.lit_inplace ? S.in + S.lit_off : S.lit;
+  ZW_LANES { // all literal runs of the batch, one per lane
+    if (lane >= cnt) continue;
+    const uint8_t* s = lit + S.seq_lp[lane];
+    uint8_t* d = S.out + S.seq_op[lane];
+    for (uint32_t i = 0, ll = S.seq_ll[lane]; i < ll; i++) d[i] = s[i];
+  }
+  ZW_SYNC();
+  for (uint32_t k = 0; k < cnt; k++) { // matches in order, the wave on each
+    const uint32_t ml = S.seq_ml[k], off = S.seq_off[k];
+    uint8_t* d = S.out + S.seq_op[k] + S.seq_ll[k];
+    const uint8_t* s = d - off;
+    ZW_LANES {
+      if (off >= ml) {
+        for (uint32_t i = lane; i < ml; i += 64) d[i] = s[i];
+      } else { // the period's bytes lie wholly below d: s[i % off]
+        uint32_t r = lane % off, st = 64 % off;
+        for (uint32_t i = lane; i < ml; i += 64) {
+          d[i] = s[r];
+          r += st;
+          if (r >= off) r -= off;
+        }
+      }
+    }
+    ZW_SYNC();
+  }
+}
+ZFN void zm_tail_literals(ZstdWave& S, const ZMemLds&, uint32_t rem, uint32_t op,
+                          uint32_t zlane) {
+  (void)zlane;
+  const uint8_t* s = (S.lit_inplace ? S.in + S.lit_off : S.lit) + S.litpos;
+  ZW_LANES { for (uint32_t i = lane; i < rem; i += 64) S.out[op + i] = s[i]; }
+  ZW_SYNC();
+}
+ZFN void zm_plain_block(ZstdWave& S, const ZMemLds&, uint32_t type, uint32_t ip,
+                        uint32_t op, uint32_t sz, uint32_t zlane) {
+  (void)zlane;
+  ZW_LANES {
+    for (uint32_t i = lane; i < sz; i += 64)
+      S.out[op + i] = S.in[type == 0 ? ip + i : ip];
+  }
+  ZW_SYNC();
+}
+
 // ---- one compressed block; false: refused
-ZFN bool zstd_block(ZstdWave& S, uint32_t cap, uint32_t zlane) {
-  ZW_LANES { if (lane == 0) zstd_lit_header(S, cap); }
+template <class ZS, class M>
+ZFN bool zstd_block(ZS& S, const M& m, uint32_t cap, uint32_t zlane) {
+  const uint8_t* in = zm_in(S, m);
+  ZW_LANES { if (lane == 0) zstd_lit_header(S, in, cap); }
   ZW_SYNC();
   if (S.fail) return false;
   if (S.need_wfse) {
     zstd_fse_build(S, S.tW, ZT_W, zlane);
-    ZW_LANES { if (lane == 0) zstd_huf_fse_weights(S); }
+    ZW_LANES { if (lane == 0) zstd_huf_fse_weights(S, in); }
     ZW_SYNC();
     if (S.fail) return false;
   }
   if (S.nstreams) {
     // a new tree's table; a treeless block decodes with the table in place
     if (S.lit_tree) zstd_huf_build(S, zlane);
-    const uint32_t ns = S.nstreams;
-    ZW_LANES { if (lane < ns) zstd_huf_stream(S, lane); }
-    ZW_SYNC();
-    if (S.fail) return false;
+    if (!zm_huf_literals(S, m, zlane)) return false;
   } else if (S.lit_fill) {
-    const uint32_t ls = S.lit_size, v = S.lit_rle;
-    ZW_LANES { for (uint32_t i = lane; i < ls; i += 64) S.lit[i] = (uint8_t)v; }
-    ZW_SYNC();
+    zm_rle_literals(S, m, zlane);
   }
-  const uint8_t* lit = S.lit_inplace ? S.in + S.lit_off : S.lit;
-  ZW_LANES { if (lane == 0) zstd_seq_header(S); }
+  ZW_LANES { if (lane == 0) zstd_seq_header(S, in); }
   ZW_SYNC();
   if (S.fail) return false;
   if (S.nseq) {
     for (uint32_t t = 0; t < 3; t++) {
-      ZW_LANES { if (lane == 0) zstd_seq_table(S, t); }
+      ZW_LANES { if (lane == 0) zstd_seq_table(S, in, t); }
       ZW_SYNC();
       if (S.fail) return false;
       if (S.build)
         zstd_fse_build(S, t == ZT_LL ? S.tLL : t == ZT_OF ? S.tOF : S.tML, t, zlane);
     }
-    ZW_LANES { if (lane == 0) zstd_seq_init(S); }
+    ZW_LANES { if (lane == 0) zstd_seq_init(S, in); }
     ZW_SYNC();
     if (S.fail) return false;
   }
   for (uint32_t left = S.nseq; left;) {
     const uint32_t cnt = left < 64 ? left : 64;
     left -= cnt;
-    ZW_LANES { if (lane == 0) zstd_seq_batch(S, cnt, left == 0); }
+    ZW_LANES { if (lane == 0) zstd_seq_batch(S, in, cnt, left == 0); }
     ZW_SYNC();
     if (S.fail) return false;
     ZW_LANES {
@@ -775,31 +866,7 @@ ZFN bool zstd_block(ZstdWave& S, uint32_t cap, uint32_t zlane) {
     }
     ZW_SYNC();
     if (S.fail) return false;
-    ZW_LANES { // all literal runs of the batch, one per lane
-      if (lane >= cnt) continue;
-      const uint8_t* s = lit + S.seq_lp[lane];
-      uint8_t* d = S.out + S.seq_op[lane];
-      for (uint32_t i = 0, ll = S.seq_ll[lane]; i < ll; i++) d[i] = s[i];
-    }
-    ZW_SYNC();
-    for (uint32_t k = 0; k < cnt; k++) { // matches in order, the wave on each
-      const uint32_t ml = S.seq_ml[k], off = S.seq_off[k];
-      uint8_t* d = S.out + S.seq_op[k] + S.seq_ll[k];
-      const uint8_t* s = d - off;
-      ZW_LANES {
-        if (off >= ml) {
-          for (uint32_t i = lane; i < ml; i += 64) d[i] = s[i];
-        } else { // the period's bytes lie wholly below d: s[i % off]
-          uint32_t r = lane % off, st = 64 % off;
-          for (uint32_t i = lane; i < ml; i += 64) {
-            d[i] = s[r];
-            r += st;
-            if (r >= off) r -= off;
-          }
-        }
-      }
-      ZW_SYNC();
-    }
+    zm_exec_batch(S, m, cnt, zlane);
     ZW_LANES {
       if (lane != cnt - 1) continue;
       S.litpos = S.seq_lp[lane] + S.seq_ll[lane];
@@ -809,43 +876,41 @@ ZFN bool zstd_block(ZstdWave& S, uint32_t cap, uint32_t zlane) {
   }
   const uint32_t rem = S.lit_size - S.litpos, op = S.op;
   if (rem > cap - op) return false;
-  {
-    const uint8_t* s = lit + S.litpos;
-    ZW_LANES { for (uint32_t i = lane; i < rem; i += 64) S.out[op + i] = s[i]; }
-  }
-  ZW_SYNC();
+  zm_tail_literals(S, m, rem, op, zlane);
   ZW_LANES { if (lane == 0) { S.op = op + rem; S.ip = S.bend; } }
   ZW_SYNC();
   return true;
 }
 
-// The frame in S.in[0, n) -> S.out[0, cap).  n, cap <= kZstdMax.  Uniform
-// result: every lane returns the same.
-ZFN bool zstd_dec_wave(ZstdWave& S, uint32_t n, uint32_t cap, uint32_t zlane) {
-  ZW_LANES { if (lane == 0) zstd_frame_header(S, n, cap); }
+// The frame of n bytes -> cap decoded bytes, both where the policy has them.
+// Uniform result: every lane returns the same.
+template <class ZS, class M>
+ZFN bool zstd_dec_frame(ZS& S, const M& m, uint32_t n, uint32_t cap, uint32_t zlane) {
+  const uint8_t* in = zm_in(S, m);
+  ZW_LANES { if (lane == 0) zstd_frame_header(S, in, n, cap); }
   ZW_SYNC();
   if (S.fail) return false;
   for (;;) {
-    ZW_LANES { if (lane == 0) zstd_block_header(S, n, cap); }
+    ZW_LANES { if (lane == 0) zstd_block_header(S, in, n, cap); }
     ZW_SYNC();
     if (S.fail) return false;
     const uint32_t type = S.btype, sz = S.bsize, ip = S.ip, op = S.op;
     if (type == 2) {
       ZSTAT(ZS_BLK_COMP);
-      if (!zstd_block(S, cap, zlane)) return false;
+      if (!zstd_block(S, m, cap, zlane)) return false;
     } else {
       ZSTAT(type == 0 ? ZS_BLK_RAW : ZS_BLK_RLE);
-      ZW_LANES {
-        for (uint32_t i = lane; i < sz; i += 64)
-          S.out[op + i] = S.in[type == 0 ? ip + i : ip];
-      }
-      ZW_SYNC();
+      zm_plain_block(S, m, type, ip, op, sz, zlane);
       ZW_LANES { if (lane == 0) { S.op = op + sz; S.ip = S.bend; } }
       ZW_SYNC();
     }
     if (S.last) break;
   }
   return S.ip == n && S.op == cap;
+}
+// The frame in S.in[0, n) -> S.out[0, cap).  n, cap <= kZstdMax.
+ZFN bool zstd_dec_wave(ZstdWave& S, uint32_t n, uint32_t cap, uint32_t zlane) {
+  return zstd_dec_frame(S, ZMemLds(), n, cap, zlane);
 }
 #endif // DCW_ZSTD_WAVE
 
