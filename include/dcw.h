@@ -57,11 +57,19 @@ enum {
                                  compress_format_version 2).  Decoded on the
                                  GPU (k_decompress_lz4) and encoded there
                                  (k_compress_lz4; one encoder, the two differ
-                                 in the block type byte only).  Blocks coded
-                                 with a preset dictionary (a file whose
-                                 metaindex names rocksdb.compression_dict)
-                                 are refused; so is LZ4 output together with
-                                 output_table_factory = 1 */
+                                 in the block type byte only).  LZ4 output
+                                 together with output_table_factory = 1 is
+                                 refused.
+                                 Preset dictionaries: type-4, -5 and -7 blocks
+                                 of an input file whose metaindex names
+                                 rocksdb.compression_dict are decoded on the
+                                 GPU with that dictionary (dcw_dict.hip;
+                                 host-only zstd blocks with
+                                 ZSTD_decompress_usingDict).  Refused: a
+                                 dictionary block that is itself stored
+                                 compressed, and, by the zstd + DZT rule,
+                                 dictionary files with zstd blocks in a job
+                                 that has DcwZipTable inputs */
 };
 
 /* ChecksumType (include/rocksdb/table.h; default kXXH3, table.h:257) */

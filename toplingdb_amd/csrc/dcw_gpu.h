@@ -35,6 +35,24 @@ struct DztFileRef {
   std::vector<DztValueIndexEntry> vblocks;
 };
 
+// Preset dictionaries of a job's input files ("rocksdb.compression_dict",
+// dcw_zstd_dict.h): one entry per file that has one, and for every entry of
+// the three work lists below its file's entry, or kNone.
+struct DictInputs {
+  static constexpr uint32_t kNone = 0xffffffffu;
+  struct Ref {
+    uint64_t off;  // absolute offset of the dictionary in the staged blob
+    uint32_t size;
+  };
+  std::vector<Ref> dicts;
+  std::vector<uint32_t> lz4, zstd, zstd_large; // parallel to the *_blocks lists
+  static bool any(const std::vector<uint32_t>& slots) {
+    for (uint32_t s : slots)
+      if (s != kNone) return true;
+    return false;
+  }
+};
+
 struct GpuInputs {
   const uint8_t* blob = nullptr; // pinned host buffer: input files concatenated
   size_t blob_size = 0;
@@ -53,6 +71,7 @@ struct GpuInputs {
   // k_decompress_zstd_large's work list
   std::vector<uint32_t> zstd_large_blocks;
   uint64_t zstd_large_stored_bytes = 0;
+  DictInputs dict;
   uint32_t checksum_type = 4;
 };
 
@@ -72,6 +91,7 @@ struct StagedInput {
   uint64_t zstd_stored_bytes = 0;
   std::vector<uint32_t> zstd_large_blocks; // as GpuInputs
   uint64_t zstd_large_stored_bytes = 0;
+  DictInputs dict; // as GpuInputs
   ~StagedInput();
 };
 
@@ -242,6 +262,9 @@ class GpuJob {
   uint64_t zstd_stored_bytes_ = 0;
   std::vector<uint32_t> zstd_large_blocks_; // k_decompress_zstd_large's
   uint64_t zstd_large_stored_bytes_ = 0;
+  DictInputs dict_; // preset dictionaries of the staged job
+  // the dictionary kernels of decode(): tables, then one launch per list
+  int dict_upload(std::string* err);
   // DZT branch of decode(): table upload, and the key-block decode
   int dzt_upload_tables(std::string* err);
   int dzt_decode_keys(bool general, std::string* err);

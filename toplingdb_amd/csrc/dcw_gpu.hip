@@ -38,6 +38,7 @@
 
 // the kernels, in pipeline order (one translation unit)
 #include "dcw_k_decode.h"
+#include "dcw_zstd_dict.h" // the launchers of dcw_dict.hip
 #include "dcw_k_merge.h"
 #include "dcw_k_emit.h"
 #include "dcw_k_filter_dzt.h"
@@ -349,6 +350,11 @@ struct GpuJob::Impl {
   DevBuf<uint32_t> d_zstdidx; // zstd input blocks (k_decompress_zstd)
   DevBuf<uint32_t> d_zstdlidx; // the large ones (k_decompress_zstd_large)
   DevBuf<uint8_t> d_zstdlit;   // its literal scratch, kZLitStride per work-group
+  // preset dictionaries (dcw_dict.hip): the job's table, the prepared zstd
+  // tables, and each work list's slots
+  DevBuf<DictDev> d_dicts;
+  DevBuf<ZstdDictTables> d_dicttabs;
+  DevBuf<uint32_t> d_lz4slot, d_zstdslot, d_zstdlslot;
   DevBuf<uint64_t> d_uoff;
   DevBuf<uint8_t> d_ublob;
   uint64_t ublob_size = 0;
@@ -548,6 +554,7 @@ void GpuJob::reset() {
   zstd_stored_bytes_ = 0;
   zstd_large_blocks_.clear();
   zstd_large_stored_bytes_ = 0;
+  dict_ = DictInputs();
   rd_frags_.clear();
   ms_decode = ms_merge = ms_dedup = ms_emit = ms_h2d = ms_d2h = 0;
 }
@@ -633,6 +640,7 @@ int GpuJob::stage(const GpuInputs& in, std::string* err) {
   zstd_stored_bytes_ = in.zstd_stored_bytes;
   zstd_large_blocks_ = in.zstd_large_blocks;
   zstd_large_stored_bytes_ = in.zstd_large_stored_bytes;
+  dict_ = in.dict;
   return 0;
 }
 
@@ -657,6 +665,7 @@ int GpuJob::stage_adopt(const StagedInput& s, std::string* err) {
   zstd_stored_bytes_ = s.zstd_stored_bytes;
   zstd_large_blocks_ = s.zstd_large_blocks;
   zstd_large_stored_bytes_ = s.zstd_large_stored_bytes;
+  dict_ = s.dict;
   if (p->arm_consts(err) != 0) return -1;
   HIPCHK(hipStreamSynchronize(p->stream));
   return 0;
@@ -680,6 +689,29 @@ int GpuJob::stage_release(StagedInput* s, std::string* err) {
   s->zstd_stored_bytes = zstd_stored_bytes_;
   s->zstd_large_blocks = zstd_large_blocks_;
   s->zstd_large_stored_bytes = zstd_large_stored_bytes_;
+  s->dict = dict_;
+  return 0;
+}
+
+// The job's dictionary table to the device, and one wave of
+// k_zstd_dict_prepare per dictionary that a GPU-decoded zstd block uses.
+int GpuJob::dict_upload(std::string* err) {
+  Impl* p = p_;
+  const uint32_t nd = (uint32_t)dict_.dicts.size();
+  std::vector<DictDev> dd(nd);
+  for (uint32_t i = 0; i < nd; i++)
+    dd[i] = {dict_.dicts[i].off, dict_.dicts[i].size, kNoDict};
+  uint32_t ntab = 0;
+  for (const auto* slots : {&dict_.zstd, &dict_.zstd_large})
+    for (uint32_t s : *slots)
+      if (s != kNoDict && dd[s].tab == kNoDict) dd[s].tab = ntab++;
+  HIPCHK(p->d_dicts.reserve(sizeof(DictDev) * nd));
+  HIPCHK(p->h2d_meta(p->d_dicts, dd.data(), sizeof(DictDev) * nd));
+  if (ntab == 0) return 0;
+  HIPCHK(p->d_dicttabs.reserve(sizeof(ZstdDictTables) * ntab));
+  p->kbegin("zstd_dict_prepare", 0);
+  launch_zstd_dict_prepare(p->stream, p->d_blob, p->d_dicts, nd, p->d_dicttabs);
+  p->kend();
   return 0;
 }
 
@@ -755,6 +787,23 @@ int GpuJob::decode(std::string* err) {
                        p->d_err, dec_pipe);
   }
   p->kend();
+  // Preset dictionaries: a work list with a block of a dictionary file goes,
+  // whole, to the dictionary variant of its kernel (dcw_dict.hip)
+  static_assert(DictInputs::kNone == kNoDict, "one value for no dictionary");
+  if (!dict_.dicts.empty() && dict_upload(err) != 0) return -1;
+  DictDecodeArgs da = {p->d_blob, p->d_boff,  p->d_bsize, p->d_uoff,
+                       p->d_usize, nullptr,   nullptr,    0,
+                       p->d_dicts, p->d_dicttabs, p->d_ublob, p->d_err, DE_ZSTD};
+  auto dict_args = [&](DevBuf<uint32_t>& d_slot, const std::vector<uint32_t>& slots,
+                       const uint32_t* d_list, uint32_t code) -> hipError_t {
+    hipError_t e = d_slot.reserve(sizeof(uint32_t) * slots.size());
+    if (e != hipSuccess) return e;
+    da.list = d_list;
+    da.slot = d_slot;
+    da.nlist = (uint32_t)slots.size();
+    da.err_code = code;
+    return p->h2d_meta(d_slot, slots.data(), sizeof(uint32_t) * slots.size());
+  };
   if (!lz4_blocks_.empty()) {
     // LZ4/LZ4HC blocks, which k_decompress skipped: one wave per listed block
     uint32_t nl = (uint32_t)lz4_blocks_.size();
@@ -762,10 +811,16 @@ int GpuJob::decode(std::string* err) {
     for (uint32_t b : lz4_blocks_) decoded += usize[b];
     HIPCHK(p->d_lz4idx.reserve(sizeof(uint32_t) * nl));
     HIPCHK(p->h2d_meta(p->d_lz4idx, lz4_blocks_.data(), sizeof(uint32_t) * nl));
+    if (DictInputs::any(dict_.lz4)) {
+      HIPCHK(dict_args(p->d_lz4slot, dict_.lz4, p->d_lz4idx, DE_LZ4));
+      p->kbegin("decompress_lz4_dict", (double)lz4_stored_bytes_ + decoded);
+      launch_decompress_lz4_dict(grid_for(nl * 64ull), p->stream, da);
+    } else {
     p->kbegin("decompress_lz4", (double)lz4_stored_bytes_ + decoded);
     hipLaunchKernelGGL(k_decompress_lz4, dim3(grid_for(nl * 64ull)), dim3(256), 0,
                        p->stream, p->d_blob, p->d_boff, p->d_bsize, p->d_uoff,
                        p->d_usize, p->d_lz4idx, nl, p->d_ublob, p->d_err);
+    }
     p->kend();
   }
   if (!zstd_blocks_.empty()) {
@@ -776,11 +831,17 @@ int GpuJob::decode(std::string* err) {
     for (uint32_t b : zstd_blocks_) decoded += usize[b];
     HIPCHK(p->d_zstdidx.reserve(sizeof(uint32_t) * nl));
     HIPCHK(p->h2d_meta(p->d_zstdidx, zstd_blocks_.data(), sizeof(uint32_t) * nl));
+    if (DictInputs::any(dict_.zstd)) {
+      HIPCHK(dict_args(p->d_zstdslot, dict_.zstd, p->d_zstdidx, DE_ZSTD));
+      p->kbegin("decompress_zstd_dict", (double)zstd_stored_bytes_ + decoded);
+      launch_decompress_zstd_dict(nl < 8192 ? nl : 8192, p->stream, da);
+    } else {
     p->kbegin("decompress_zstd", (double)zstd_stored_bytes_ + decoded);
     hipLaunchKernelGGL(k_decompress_zstd, dim3(nl < 8192 ? nl : 8192),
                        dim3(WAVE), 0, p->stream, p->d_blob, p->d_boff,
                        p->d_bsize, p->d_uoff, p->d_usize, p->d_zstdidx, nl,
                        p->d_ublob, p->d_err);
+    }
     p->kend();
   }
   if (!zstd_large_blocks_.empty()) {
@@ -797,11 +858,18 @@ int GpuJob::decode(std::string* err) {
     HIPCHK(p->h2d_meta(p->d_zstdlidx, zstd_large_blocks_.data(),
                        sizeof(uint32_t) * nl));
     HIPCHK(p->d_zstdlit.reserve((size_t)grid * kZLitStride));
+    if (DictInputs::any(dict_.zstd_large)) {
+      HIPCHK(dict_args(p->d_zstdlslot, dict_.zstd_large, p->d_zstdlidx, DE_ZSTD));
+      p->kbegin("decompress_zstd_large_dict",
+                (double)zstd_large_stored_bytes_ + decoded);
+      launch_decompress_zstd_large_dict(grid, p->stream, da, p->d_zstdlit);
+    } else {
     p->kbegin("decompress_zstd_large", (double)zstd_large_stored_bytes_ + decoded);
     launch_decompress_zstd_large(grid, p->stream, p->d_blob, p->d_boff,
                                  p->d_bsize, p->d_uoff, p->d_usize,
                                  p->d_zstdlidx, nl, p->d_ublob, p->d_zstdlit,
                                  p->d_err, DE_ZSTD);
+    }
     p->kend();
   }
   if (n_dvb) {

@@ -354,8 +354,8 @@ ParsedSst parse_sst(const uint8_t* data, size_t size) {
       const uint8_t* mp = mb;
       const uint8_t* ml = mb + mend;
       std::string mkey;
-      uint64_t rd_off = 0, rd_sz = 0;
-      bool rd_found = false;
+      uint64_t rd_off = 0, rd_sz = 0, cd_off = 0, cd_sz = 0;
+      bool rd_found = false, cd_found = false;
       while (mp < ml) {
         uint32_t sh, ns, vl;
         if ((a = varint32_get(mp, ml, &sh)) < 0) break;
@@ -369,10 +369,10 @@ ParsedSst parse_sst(const uint8_t* data, size_t size) {
         mkey.append((const char*)mp, ns);
         mp += ns;
         if (mkey == "rocksdb.compression_dict") {
-          // blocks coded against a preset dictionary: no decoder here has it
-          r.error = "dictionary-compressed blocks (rocksdb.compression_dict) "
-                    "unsupported";
-          return r;
+          const uint8_t* vp = mp;
+          int b1 = varint64_get(vp, mp + vl, &cd_off);
+          if (b1 > 0 && varint64_get(vp + b1, mp + vl, &cd_sz) > 0)
+            cd_found = true;
         }
         if (mkey == "rocksdb.range_del") {
           const uint8_t* vp = mp;
@@ -381,6 +381,28 @@ ParsedSst parse_sst(const uint8_t* data, size_t size) {
             rd_found = true;
         }
         mp += vl;
+      }
+      // the preset dictionary of the data blocks: written uncompressed
+      // (block_based_table_builder.cc:1712-1733, kNoCompression) and read
+      // back whole as the UncompressionDict (block_based_table_reader.cc:1096)
+      if (cd_found && cd_sz != 0) {
+        if (cd_sz > 0x7fffffffu || cd_off > size || cd_sz + kTrailerSize > size - cd_off) {
+          r.error = "compression_dict block handle out of range";
+          return r;
+        }
+        const uint8_t* cb = data + cd_off;
+        if (cb[cd_sz] != 0) {
+          r.error = "compression_dict block stored compressed: unsupported";
+          return r;
+        }
+        if (r.checksum_type != 0 &&
+            load32(cb + cd_sz + 1) !=
+                block_checksum(r.checksum_type, &g_crc, cb, cd_sz, 0)) {
+          r.error = "compression_dict block checksum mismatch";
+          return r;
+        }
+        r.dict_off = cd_off;
+        r.dict_size = cd_sz;
       }
       if (rd_found && rd_off + rd_sz + kTrailerSize <= size && rd_sz >= 8) {
         const uint8_t* rb = data + rd_off;

@@ -89,6 +89,9 @@ struct ParsedSst {
   uint32_t checksum_type = 4;
   std::vector<SstIndexEntry> data_blocks;
   std::vector<SstTombstone> tombstones; // "rocksdb.range_del" meta block
+  // "rocksdb.compression_dict" meta block: the preset dictionary of the
+  // file's type-4, -5 and -7 data blocks; size 0: none
+  uint64_t dict_off = 0, dict_size = 0;
   std::string error;
   bool ok = false;
 };

@@ -28,9 +28,11 @@
 #if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
 #include <hip/hip_runtime.h>
 #define DCW_LZ4_FN __host__ __device__ inline
+#define DCW_LZ4_FN_M __host__ __device__
 #define DCW_LZ4_LDS 1
 #else
 #define DCW_LZ4_FN static inline
+#define DCW_LZ4_FN_M
 #ifdef DCW_LZ4_LDS_ON_HOST
 #define DCW_LZ4_LDS 1
 #endif
@@ -53,6 +55,35 @@ DCW_LZ4_FN int lz4_preamble(const uint8_t* p, uint32_t n, uint32_t* usize) {
     }
   }
   return -1;
+}
+
+// A preset dictionary (util/compression.h:1189-1196: LZ4_setStreamDecode with
+// the file's "rocksdb.compression_dict" block, then
+// LZ4_decompress_safe_continue): its bytes count as output produced before the
+// block's first byte, so an offset may reach back into the dictionary's tail.
+// Offsets have 16 bits: only the last 65535 bytes can be reached.  Both
+// decoders below take the dictionary as a last argument; Lz4NoDict, the
+// default, folds away and leaves them what they are without one.
+struct Lz4NoDict {
+  static constexpr uint32_t len() { return 0; }
+  static constexpr const uint8_t* end() { return nullptr; }
+};
+struct Lz4Dict {
+  const uint8_t* e; // one past the dictionary's last byte
+  uint32_t n;       // min(size, 65535)
+  DCW_LZ4_FN_M uint32_t len() const { return n; }
+  DCW_LZ4_FN_M const uint8_t* end() const { return e; }
+};
+// The part of a match at out[op] that lies in the dictionary (offset > op;
+// offset <= op + len was checked): bytes moved.  What is left is the usual
+// move at the same offset, whose source is then out[0].
+template <class D>
+DCW_LZ4_FN uint32_t lz4_dict_part(const D& dict, uint8_t* out, uint32_t op,
+                                  uint32_t offset, uint32_t ml) {
+  const uint32_t need = offset - op, c = need < ml ? need : ml;
+  const uint8_t* s = dict.end() - need;
+  for (uint32_t i = 0; i < c; i++) out[op + i] = s[i];
+  return c;
 }
 
 #ifdef DCW_LZ4_LDS
@@ -106,8 +137,10 @@ __device__ __forceinline__ bool lz4_ext_win(const uint8_t* in, uint32_t n,
 // up to 15 B past the output end, literal loads up to 15 B and header
 // fetches up to 7 B past the input end: all inside DEC_PAD.  Every accept
 // or refuse decision is taken against the true n and cap before the move.
+template <class D = Lz4NoDict>
 __device__ inline bool lz4_dec_lds(const uint8_t* __restrict__ in, uint32_t n,
-                            uint8_t* __restrict__ out, uint32_t cap) {
+                            uint8_t* __restrict__ out, uint32_t cap,
+                            const D& dict = D()) {
   uint32_t ip = 0, op = 0;
   while (ip < n) {
     uint64_t h = lds_ld64(in + ip);
@@ -138,7 +171,13 @@ __device__ inline bool lz4_dec_lds(const uint8_t* __restrict__ in, uint32_t n,
     uint32_t offset = (uint32_t)(h >> (8 * (at - hb))) & 0xffffu;
     ip += 2;
     if (ml == 19 && !lz4_ext_win(in, n, h, hb, ip, ml, cap - op)) return false;
-    if (offset == 0 || offset > op || ml > cap - op) return false;
+    if (offset == 0 || offset > op + dict.len() || ml > cap - op) return false;
+    if (offset > op) { // never without a dictionary
+      uint32_t c = lz4_dict_part(dict, out, op, offset, ml);
+      op += c;
+      ml -= c;
+      if (ml == 0) continue;
+    }
     uint32_t src = op - offset;
     uint32_t end = op + ml;
     if (offset >= 16) {
@@ -177,8 +216,9 @@ __device__ inline bool lz4_dec_lds(const uint8_t* __restrict__ in, uint32_t n,
 // Generic byte-exact form: touches in[0, n) and out[0, cap) only.  The GPU
 // uses it global to global for blocks beyond DEC_MAX; the host uses the
 // same function (index blocks in parse_sst).
-DCW_LZ4_FN bool lz4_dec(const uint8_t* in, uint32_t n, uint8_t* out,
-                        uint32_t cap) {
+template <class D = Lz4NoDict>
+DCW_LZ4_FN bool lz4_dec(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap,
+                        const D& dict = D()) {
   if ((n | cap) >> 31) return false; // keeps the 32-bit length sums exact
   uint32_t ip = 0, op = 0;
   while (ip < n) {
@@ -216,7 +256,12 @@ DCW_LZ4_FN bool lz4_dec(const uint8_t* in, uint32_t n, uint8_t* out,
         if (ml > cap - op) return false;
       } while (b == 255);
     }
-    if (offset == 0 || offset > op || ml > cap - op) return false;
+    if (offset == 0 || offset > op + dict.len() || ml > cap - op) return false;
+    if (offset > op) { // never without a dictionary
+      uint32_t c = lz4_dict_part(dict, out, op, offset, ml);
+      op += c;
+      ml -= c;
+    }
     const uint8_t* s = out + op - offset;
     i = 0;
     if (offset >= 8)

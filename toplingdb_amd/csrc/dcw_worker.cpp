@@ -280,6 +280,10 @@ struct LoadedInputs {
 // to the device as raw blocks with recomputed trailers.
 extern "C" size_t ZSTD_decompress(void*, size_t, const void*, size_t);
 extern "C" unsigned ZSTD_isError(size_t);
+extern "C" void* ZSTD_createDCtx(void);
+extern "C" size_t ZSTD_freeDCtx(void*);
+extern "C" size_t ZSTD_decompress_usingDict(void*, void*, size_t, const void*,
+                                            size_t, const void*, size_t);
 
 int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
                 GpuJob* job) {
@@ -304,6 +308,10 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
   L->us_stage += now_usec() - tphase;
   L->gi.run_block_begin.push_back(0);
   uint32_t cstype = 0xffffffff;
+  // per block: its file's entry of gi.dict.dicts (a file with a
+  // "rocksdb.compression_dict" block), or kNone
+  std::vector<uint32_t> blk_dict;
+  DictInputs& DI = L->gi.dict;
   for (uint32_t r = 0; r < d->num_runs; r++) {
     for (uint32_t f = 0; f < d->runs[r].num_files; f++) {
       const char* path = d->runs[r].files[f];
@@ -423,6 +431,10 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
       }
       for (auto& h : ps.data_blocks)
         L->gi.blocks.push_back({base + h.off, (uint32_t)h.size});
+      if (ps.dict_size) DI.dicts.push_back({base + ps.dict_off, (uint32_t)ps.dict_size});
+      blk_dict.resize(L->gi.blocks.size(), ps.dict_size
+                                               ? (uint32_t)DI.dicts.size() - 1
+                                               : DictInputs::kNone);
       for (auto& t : ps.tombstones) L->tombstones.push_back(t);
       L->in_bytes += sz;
     }
@@ -457,19 +469,24 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
     uint8_t type = L->blob.p[blk.off + blk.size];
     if (type == 7) {
       any_zstd = true;
-      if (!zstd_on_host && zstd_eligible(L->blob.p + blk.off, blk.size)) {
+      // a block of a dictionary file may carry a Dictionary_ID field
+      const bool dict = blk_dict[bi] != DictInputs::kNone;
+      if (!zstd_on_host && zstd_eligible(L->blob.p + blk.off, blk.size, dict)) {
         L->gi.zstd_blocks.push_back((uint32_t)bi);
         L->gi.zstd_stored_bytes += blk.size;
+        DI.zstd.push_back(blk_dict[bi]);
       } else if (!zstd_large_on_host &&
-                 zstd_eligible_large(L->blob.p + blk.off, blk.size)) {
+                 zstd_eligible_large(L->blob.p + blk.off, blk.size, dict)) {
         L->gi.zstd_large_blocks.push_back((uint32_t)bi);
         L->gi.zstd_large_stored_bytes += blk.size;
+        DI.zstd_large.push_back(blk_dict[bi]);
       } else {
         any_host_zstd = true;
       }
     } else if (type == 4 || type == 5) {
       L->gi.lz4_blocks.push_back((uint32_t)bi);
       L->gi.lz4_stored_bytes += blk.size;
+      DI.lz4.push_back(blk_dict[bi]);
     }
   }
   L->us_parse += now_usec() - tphase;
@@ -485,6 +502,21 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
     RawBuf nb;
     uint64_t est = L->blob.len * 2 + (16u << 20);
     nb.reserve(est);
+    // the dictionaries go first: the blocks that stay compressed still need
+    // them on the device, and host-only blocks of their files are decoded
+    // with them here as the reference does (util/compression.h:1413,
+    // ZSTD_decompress_usingDict).  The old blob lives until the swap below.
+    std::vector<const uint8_t*> old_dict;
+    for (auto& dr : DI.dicts) {
+      old_dict.push_back(L->blob.p + dr.off);
+      dr.off = nb.len;
+      nb.append(old_dict.back(), dr.size);
+    }
+    void* dctx = DI.dicts.empty() ? nullptr : ZSTD_createDCtx();
+    struct DctxFree {
+      void* c;
+      ~DctxFree() { if (c) ZSTD_freeDCtx(c); }
+    } dctx_free{dctx};
     size_t zi = 0, zli = 0; // next GPU-decoded zstd block of either list
     for (size_t bi = 0; bi < L->gi.blocks.size(); bi++) {
       BlockRef& blk = L->gi.blocks[bi];
@@ -512,8 +544,12 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
           return -1;
         }
         nb.reserve(nb.len + un + 8);
-        size_t got = ZSTD_decompress(nb.p + nb.len, un, body + hn,
-                                     blk.size - hn);
+        const uint32_t ds = blk_dict[bi];
+        size_t got = ds == DictInputs::kNone
+                         ? ZSTD_decompress(nb.p + nb.len, un, body + hn, blk.size - hn)
+                         : ZSTD_decompress_usingDict(dctx, nb.p + nb.len, un, body + hn,
+                                                     blk.size - hn, old_dict[ds],
+                                                     DI.dicts[ds].size);
         if (ZSTD_isError(got) || got != un) {
           *err = "zstd input block corrupt";
           return -1;

@@ -66,8 +66,11 @@ ZHD int zstd_preamble(const uint8_t* p, uint32_t n, uint32_t* usize) {
 // The eligibility walk over a stored type-7 block: preamble, magic, no
 // dictionary ID, no content checksum, reserved bit clear, the block headers
 // chain exactly to the end of the payload as one frame, stored and promised
-// size within kZstdMax.  Touches p[0, n) only.
-ZHD bool zstd_eligible(const uint8_t* p, uint32_t n) {
+// size within kZstdMax.  Touches p[0, n) only.  `dict`: the block's file has a
+// dictionary (dcw_zstd_dict.h), so a Dictionary_ID field of 1, 2 or 4 bytes
+// may stand behind the window descriptor.
+ZHD uint32_t zstd_did_bytes(uint32_t fhd) { return (fhd & 3) == 3 ? 4 : fhd & 3; }
+ZHD bool zstd_eligible(const uint8_t* p, uint32_t n, bool dict = false) {
   uint32_t un;
   int hn = zstd_preamble(p, n, &un);
   if (hn < 0 || un > kZstdMax || n - (uint32_t)hn > kZstdMax) return false;
@@ -77,9 +80,10 @@ ZHD bool zstd_eligible(const uint8_t* p, uint32_t n) {
   uint32_t magic;
   memcpy(&magic, p, 4);
   uint32_t fhd = p[4];
-  if (magic != kZstdMagic || (fhd & 0x0f)) return false;
+  if (magic != kZstdMagic || (fhd & (dict ? 0x0c : 0x0f))) return false;
   uint32_t fcs = fhd >> 6, single = (fhd >> 5) & 1;
-  uint32_t ip = 5 + !single + (fcs == 0 ? single : fcs == 1 ? 2 : fcs == 2 ? 4 : 8);
+  uint32_t ip = 5 + !single + (fcs == 0 ? single : fcs == 1 ? 2 : fcs == 2 ? 4 : 8) +
+                zstd_did_bytes(fhd);
   for (;;) {
     if (ip + 3 > n) return false;
     uint32_t h = p[ip] | (p[ip + 1] << 8) | ((uint32_t)p[ip + 2] << 16);
@@ -169,8 +173,22 @@ struct alignas(16) ZstdWave {
 //   zm_exec_batch          literal runs and matches of a placed batch
 //   zm_tail_literals       the literals behind the last sequence
 //   zm_plain_block         a raw or RLE block
+// A policy may carry a preset dictionary too (dcw_zstd_dict.h).  The hooks for
+// that have the defaults below, "no dictionary", which fold away:
+//   zm_has_dict(m)         a Dictionary_ID field may stand in the frame header
+//   zm_dict_id(m)          what a nonzero one must equal
+//   zm_prefix_len(m)       bytes of dictionary content before output byte 0
+//   zm_frame_begin         the dictionary's tables into S, behind the header
+//   zm_dict_part           the part of a match that lies in the dictionary
 struct ZMemLds {};
 ZFN const uint8_t* zm_in(const ZstdWave& S, const ZMemLds&) { return S.in; }
+template <class M> ZFN constexpr bool zm_has_dict(const M&) { return false; }
+template <class M> ZFN constexpr uint32_t zm_dict_id(const M&) { return 0; }
+template <class M> ZFN constexpr uint32_t zm_prefix_len(const M&) { return 0; }
+template <class ZS, class M> ZFN void zm_frame_begin(ZS&, const M&, uint32_t) {}
+template <class M>
+ZFN constexpr uint32_t zm_dict_part(const M&, uint8_t*, uint32_t, uint32_t, uint32_t,
+                                    uint32_t) { return 0; }
 ZFN uint8_t* zm_wscr(ZstdWave& S) { return S.lit; }
 
 ZFN uint32_t z_highbit(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
@@ -511,8 +529,9 @@ ZFN void zstd_lit_streams(ZS& S, const uint8_t* in) {
 }
 
 // ---- headers (lane 0)
-template <class ZS>
-ZFN void zstd_frame_header(ZS& S, const uint8_t* in, uint32_t n, uint32_t cap) {
+template <class ZS, class M>
+ZFN void zstd_frame_header(ZS& S, const M& m, const uint8_t* in, uint32_t n,
+                           uint32_t cap) {
   S.fail = 0; S.op = 0; S.last = 0;
   S.have_huf = S.have_fse = 0;
   S.rep1 = 1; S.rep2 = 4; S.rep3 = 8;
@@ -521,12 +540,23 @@ ZFN void zstd_frame_header(ZS& S, const uint8_t* in, uint32_t n, uint32_t cap) {
   uint32_t magic;
   memcpy(&magic, p, 4);
   uint32_t fhd = p[4], fcs = fhd >> 6, single = (fhd >> 5) & 1;
-  // dictionary ID, content checksum, reserved bit: none of them here
-  if (magic != kZstdMagic || (fhd & 0x0f)) { S.fail = 1; return; }
+  // content checksum, reserved bit: none of them here; a dictionary ID only
+  // where the policy has a dictionary
+  if (magic != kZstdMagic || (fhd & (zm_has_dict(m) ? 0x0c : 0x0f))) {
+    S.fail = 1;
+    return;
+  }
   uint32_t ip = 5;
   if (!single) {
     if ((uint32_t)(p[ip] >> 3) + 10 > 31) { S.fail = 1; return; }
     ip++;
+  }
+  if (zm_has_dict(m) && (fhd & 3)) { // nonzero: the dictionary's, as libzstd
+    uint32_t dl = zstd_did_bytes(fhd), id = 0;  // (ZSTD_decodeFrameHeader)
+    if (ip + dl > n) { S.fail = 1; return; }
+    for (uint32_t k = 0; k < dl; k++) id |= (uint32_t)p[ip + k] << (8 * k);
+    if (id && id != zm_dict_id(m)) { S.fail = 1; return; }
+    ip += dl;
   }
   uint32_t fb = fcs == 0 ? single : fcs == 1 ? 2 : fcs == 2 ? 4 : 8;
   if (ip + fb > n) { S.fail = 1; return; }
@@ -554,6 +584,36 @@ ZFN void zstd_block_header(ZS& S, const uint8_t* in, uint32_t n, uint32_t cap) {
       (type == 2 && sz == kZstdBlockMax)) { S.fail = 1; return; }
   S.ip = ip;
   S.bend = ip + stored;
+}
+// A Huffman tree description at in[at], of at most lim bytes (lane 0): the
+// weights, or for FSE-compressed weights need_wfse and where their stream
+// lies.  -> its size, 0: refuse
+template <class ZS>
+ZFN uint32_t zstd_huf_tree_desc(ZS& S, const uint8_t* in, uint32_t at, uint32_t lim) {
+  if (lim == 0) return 0;
+  uint32_t hb = in[at], desc;
+  uint8_t* W = zm_wscr(S);
+  if (hb >= 128) { // direct 4-bit weights
+    ZSTAT(ZS_W_DIRECT);
+    uint32_t nw = hb - 127;
+    desc = 1 + ((nw + 1) >> 1);
+    if (desc > lim) return 0;
+    for (uint32_t i = 0; i < nw; i++) {
+      uint32_t b = in[at + 1 + (i >> 1)];
+      W[i] = (uint8_t)((i & 1) ? (b & 15) : (b >> 4));
+    }
+    zstd_huf_weights_done(S, nw);
+  } else { // FSE-compressed weights: description now, stream after the build
+    ZSTAT(ZS_W_FSE);
+    desc = 1 + hb;
+    if (hb == 0 || desc > lim) return 0;
+    uint32_t c = zstd_read_ncount(S, in + at + 1, hb, 11, 6);
+    if (c == 0 || c >= hb) return 0;
+    S.need_wfse = 1;
+    S.ws_start = at + 1 + c;
+    S.ws_len = hb - c;
+  }
+  return S.fail ? 0 : desc;
 }
 template <class ZS>
 ZFN void zstd_lit_header(ZS& S, const uint8_t* in, uint32_t cap) {
@@ -605,30 +665,10 @@ ZFN void zstd_lit_header(ZS& S, const uint8_t* in, uint32_t cap) {
     return;
   }
   S.have_huf = 1;
-  uint32_t hb = in[at], desc;
-  uint8_t* W = zm_wscr(S);
-  if (hb >= 128) { // direct 4-bit weights
-    ZSTAT(ZS_W_DIRECT);
-    uint32_t nw = hb - 127;
-    desc = 1 + ((nw + 1) >> 1);
-    if (desc >= cs) { S.fail = 1; return; }
-    for (uint32_t i = 0; i < nw; i++) {
-      uint32_t b = in[at + 1 + (i >> 1)];
-      W[i] = (uint8_t)((i & 1) ? (b & 15) : (b >> 4));
-    }
-    zstd_huf_weights_done(S, nw);
-  } else { // FSE-compressed weights: description now, stream after the build
-    ZSTAT(ZS_W_FSE);
-    desc = 1 + hb;
-    if (hb == 0 || desc >= cs) { S.fail = 1; return; }
-    uint32_t c = zstd_read_ncount(S, in + at + 1, hb, 11, 6);
-    if (c == 0 || c >= hb) { S.fail = 1; return; }
-    S.need_wfse = 1;
-    S.ws_start = at + 1 + c;
-    S.ws_len = hb - c;
-  }
+  const uint32_t desc = zstd_huf_tree_desc(S, in, at, cs - 1);
+  if (desc == 0) { S.fail = 1; return; }
   S.hs_rs = at + desc; S.hs_rl = cs - desc;
-  if (!S.fail) zstd_lit_streams(S, in);
+  zstd_lit_streams(S, in);
 }
 template <class ZS>
 ZFN void zstd_seq_header(ZS& S, const uint8_t* in) {
@@ -761,7 +801,8 @@ ZFN void zm_rle_literals(ZstdWave& S, const ZMemLds&, uint32_t zlane) {
   ZW_LANES { for (uint32_t i = lane; i < ls; i += 64) S.lit[i] = (uint8_t)v; }
   ZW_SYNC();
 }
-ZFN void zm_exec_batch(ZstdWave& S, const ZMemLds&, uint32_t cnt, uint32_t zlane) {
+template <class M>
+ZFN void zm_exec_batch(ZstdWave& S, const M& m, uint32_t cnt, uint32_t zlane) {
   (void)zlane;
   const uint8_t* lit = S.lit_inplace ? S.in + S.lit_off : S.lit;
   ZW_LANES { // all literal runs of the batch, one per lane
@@ -772,8 +813,12 @@ ZFN void zm_exec_batch(ZstdWave& S, const ZMemLds&, uint32_t cnt, uint32_t zlane
   }
   ZW_SYNC();
   for (uint32_t k = 0; k < cnt; k++) { // matches in order, the wave on each
-    const uint32_t ml = S.seq_ml[k], off = S.seq_off[k];
-    uint8_t* d = S.out + S.seq_op[k] + S.seq_ll[k];
+    uint32_t ml = S.seq_ml[k];
+    const uint32_t off = S.seq_off[k], at = S.seq_op[k] + S.seq_ll[k];
+    uint8_t* d = S.out + at;
+    const uint32_t pre = zm_dict_part(m, d, at, off, ml, zlane);
+    d += pre;
+    ml -= pre;
     const uint8_t* s = d - off;
     ZW_LANES {
       if (off >= ml) {
@@ -859,7 +904,7 @@ ZFN bool zstd_block(ZS& S, const M& m, uint32_t cap, uint32_t zlane) {
       uint32_t lp = S.litpos + (uint32_t)S.scan[lane];
       uint32_t o = S.op + (uint32_t)(S.scan[lane] >> 32);
       if (lp > S.lit_size || ll > S.lit_size - lp || o > cap || ll + ml > cap - o ||
-          S.seq_off[lane] > o + ll)
+          S.seq_off[lane] > o + ll + zm_prefix_len(m))
         S.fail = 1;
       S.seq_lp[lane] = lp;
       S.seq_op[lane] = o;
@@ -887,9 +932,10 @@ ZFN bool zstd_block(ZS& S, const M& m, uint32_t cap, uint32_t zlane) {
 template <class ZS, class M>
 ZFN bool zstd_dec_frame(ZS& S, const M& m, uint32_t n, uint32_t cap, uint32_t zlane) {
   const uint8_t* in = zm_in(S, m);
-  ZW_LANES { if (lane == 0) zstd_frame_header(S, in, n, cap); }
+  ZW_LANES { if (lane == 0) zstd_frame_header(S, m, in, n, cap); }
   ZW_SYNC();
   if (S.fail) return false;
+  zm_frame_begin(S, m, zlane);
   for (;;) {
     ZW_LANES { if (lane == 0) zstd_block_header(S, in, n, cap); }
     ZW_SYNC();

@@ -42,8 +42,8 @@ namespace dcw {
 // kZstdMax bounds.  One plain frame (no dictionary ID, no content checksum,
 // reserved bit clear) whose block headers chain exactly to the end of the
 // payload, no Block_Size over 128 KiB, promised size at most 0x7fffffff.
-// Touches p[0, n) only.
-ZHD bool zstd_eligible_large(const uint8_t* p, uint32_t n) {
+// Touches p[0, n) only.  `dict` as for zstd_eligible().
+ZHD bool zstd_eligible_large(const uint8_t* p, uint32_t n, bool dict = false) {
   uint32_t un;
   int hn = zstd_preamble(p, n, &un);
   if (hn < 0 || un > 0x7fffffffu) return false;
@@ -53,9 +53,10 @@ ZHD bool zstd_eligible_large(const uint8_t* p, uint32_t n) {
   uint32_t magic;
   memcpy(&magic, p, 4);
   uint32_t fhd = p[4];
-  if (magic != kZstdMagic || (fhd & 0x0f)) return false;
+  if (magic != kZstdMagic || (fhd & (dict ? 0x0c : 0x0f))) return false;
   uint32_t fcs = fhd >> 6, single = (fhd >> 5) & 1;
-  uint32_t ip = 5 + !single + (fcs == 0 ? single : fcs == 1 ? 2 : fcs == 2 ? 4 : 8);
+  uint32_t ip = 5 + !single + (fcs == 0 ? single : fcs == 1 ? 2 : fcs == 2 ? 4 : 8) +
+                zstd_did_bytes(fhd);
   for (;;) {
     if (ip + 3 > n) return false;
     uint32_t h = p[ip] | (p[ip + 1] << 8) | ((uint32_t)p[ip + 2] << 16);
@@ -204,8 +205,8 @@ ZFN const uint8_t* zl_literals(const ZstdLargeLds& S, const ZMemGlobal& m) {
 
 // A placed batch: seq_lp/seq_op hold where each run of literals starts in
 // the literals and in the output; every bound has been checked.
-ZFN void zm_exec_batch(ZstdLargeLds& S, const ZMemGlobal& m, uint32_t cnt,
-                       uint32_t zlane) {
+template <class M>
+ZFN void zm_exec_batch(ZstdLargeLds& S, const M& m, uint32_t cnt, uint32_t zlane) {
   (void)zlane;
   const uint8_t* lit = zl_literals(S, m);
   const uint32_t fill = S.lit_fill, rle = S.lit_rle, lit0 = S.litpos;
@@ -223,8 +224,12 @@ ZFN void zm_exec_batch(ZstdLargeLds& S, const ZMemGlobal& m, uint32_t cnt,
   }
   ZW_SYNC();
   for (uint32_t k = 0; k < cnt; k++) { // matches in order, the wave on each
-    const uint32_t ml = S.seq_ml[k], off = S.seq_off[k];
-    uint8_t* d = m.out + S.seq_op[k] + S.seq_ll[k];
+    uint32_t ml = S.seq_ml[k];
+    const uint32_t off = S.seq_off[k], at = S.seq_op[k] + S.seq_ll[k];
+    uint8_t* d = m.out + at;
+    const uint32_t pre = zm_dict_part(m, d, at, off, ml, zlane);
+    d += pre;
+    ml -= pre;
     const uint8_t* s = d - off;
     if (off >= ml && ml >= 128) {
       ZL_COPY(d, s, ml)
