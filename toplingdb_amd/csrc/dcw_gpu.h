@@ -71,6 +71,9 @@ struct GpuInputs {
   // k_decompress_zstd_large's work list
   std::vector<uint32_t> zstd_large_blocks;
   uint64_t zstd_large_stored_bytes = 0;
+  // and for the zlib blocks (type 2): k_decompress_zlib's work list
+  std::vector<uint32_t> zlib_blocks;
+  uint64_t zlib_stored_bytes = 0;
   DictInputs dict;
   uint32_t checksum_type = 4;
 };
@@ -91,6 +94,8 @@ struct StagedInput {
   uint64_t zstd_stored_bytes = 0;
   std::vector<uint32_t> zstd_large_blocks; // as GpuInputs
   uint64_t zstd_large_stored_bytes = 0;
+  std::vector<uint32_t> zlib_blocks; // as GpuInputs
+  uint64_t zlib_stored_bytes = 0;
   DictInputs dict; // as GpuInputs
   ~StagedInput();
 };
@@ -258,6 +263,8 @@ class GpuJob {
   std::vector<DztFileRef> dzt_files_; // DZT inputs of the staged job
   std::vector<uint32_t> lz4_blocks_;  // LZ4 blocks of the staged job
   uint64_t lz4_stored_bytes_ = 0;
+  std::vector<uint32_t> zlib_blocks_; // zlib blocks of the staged job
+  uint64_t zlib_stored_bytes_ = 0;
   std::vector<uint32_t> zstd_blocks_; // GPU-decoded zstd blocks of the job
   uint64_t zstd_stored_bytes_ = 0;
   std::vector<uint32_t> zstd_large_blocks_; // k_decompress_zstd_large's

@@ -347,6 +347,7 @@ struct GpuJob::Impl {
   DevBuf<uint32_t> d_usize;
   DevBuf<uint8_t> d_btype_in;
   DevBuf<uint32_t> d_lz4idx; // LZ4/LZ4HC input blocks (k_decompress_lz4)
+  DevBuf<uint32_t> d_zlibidx; // zlib input blocks (k_decompress_zlib)
   DevBuf<uint32_t> d_zstdidx; // zstd input blocks (k_decompress_zstd)
   DevBuf<uint32_t> d_zstdlidx; // the large ones (k_decompress_zstd_large)
   DevBuf<uint8_t> d_zstdlit;   // its literal scratch, kZLitStride per work-group
@@ -480,6 +481,8 @@ struct GpuJob::Impl {
       if (err) *err = std::string(what) + " failed, code " + std::to_string(e);
       if (err && e == DE_LZ4)
         *err += " (DE_LZ4: bad LZ4/LZ4HC preamble or stream in an input block)";
+      if (err && e == DE_ZLIB)
+        *err += " (DE_ZLIB: bad zlib preamble or deflate stream in an input block)";
       if (err && e == DE_ZSTD)
         *err += " (DE_ZSTD: bad zstd preamble or frame in an input block)";
       return -1;
@@ -550,6 +553,8 @@ void GpuJob::reset() {
   dzt_files_.clear();
   lz4_blocks_.clear();
   lz4_stored_bytes_ = 0;
+  zlib_blocks_.clear();
+  zlib_stored_bytes_ = 0;
   zstd_blocks_.clear();
   zstd_stored_bytes_ = 0;
   zstd_large_blocks_.clear();
@@ -636,6 +641,8 @@ int GpuJob::stage(const GpuInputs& in, std::string* err) {
   dzt_files_ = in.dzt_files;
   lz4_blocks_ = in.lz4_blocks;
   lz4_stored_bytes_ = in.lz4_stored_bytes;
+  zlib_blocks_ = in.zlib_blocks;
+  zlib_stored_bytes_ = in.zlib_stored_bytes;
   zstd_blocks_ = in.zstd_blocks;
   zstd_stored_bytes_ = in.zstd_stored_bytes;
   zstd_large_blocks_ = in.zstd_large_blocks;
@@ -661,6 +668,8 @@ int GpuJob::stage_adopt(const StagedInput& s, std::string* err) {
   dzt_files_ = s.dzt_files;
   lz4_blocks_ = s.lz4_blocks;
   lz4_stored_bytes_ = s.lz4_stored_bytes;
+  zlib_blocks_ = s.zlib_blocks;
+  zlib_stored_bytes_ = s.zlib_stored_bytes;
   zstd_blocks_ = s.zstd_blocks;
   zstd_stored_bytes_ = s.zstd_stored_bytes;
   zstd_large_blocks_ = s.zstd_large_blocks;
@@ -685,6 +694,8 @@ int GpuJob::stage_release(StagedInput* s, std::string* err) {
   s->dzt_files = dzt_files_;
   s->lz4_blocks = lz4_blocks_;
   s->lz4_stored_bytes = lz4_stored_bytes_;
+  s->zlib_blocks = zlib_blocks_;
+  s->zlib_stored_bytes = zlib_stored_bytes_;
   s->zstd_blocks = zstd_blocks_;
   s->zstd_stored_bytes = zstd_stored_bytes_;
   s->zstd_large_blocks = zstd_large_blocks_;
@@ -821,6 +832,20 @@ int GpuJob::decode(std::string* err) {
                        p->stream, p->d_blob, p->d_boff, p->d_bsize, p->d_uoff,
                        p->d_usize, p->d_lz4idx, nl, p->d_ublob, p->d_err);
     }
+    p->kend();
+  }
+  if (!zlib_blocks_.empty()) {
+    // zlib blocks, which k_decompress skipped: one wave (one work-group: the
+    // decoder's LDS) per listed block
+    uint32_t nl = (uint32_t)zlib_blocks_.size();
+    double decoded = 0;
+    for (uint32_t b : zlib_blocks_) decoded += usize[b];
+    HIPCHK(p->d_zlibidx.reserve(sizeof(uint32_t) * nl));
+    HIPCHK(p->h2d_meta(p->d_zlibidx, zlib_blocks_.data(), sizeof(uint32_t) * nl));
+    p->kbegin("decompress_zlib", (double)zlib_stored_bytes_ + decoded);
+    launch_decompress_zlib(nl < 8192 ? nl : 8192, p->stream, p->d_blob, p->d_boff,
+                           p->d_bsize, p->d_uoff, p->d_usize, p->d_zlibidx, nl,
+                           p->d_ublob, p->d_err, DE_ZLIB);
     p->kend();
   }
   if (!zstd_blocks_.empty()) {

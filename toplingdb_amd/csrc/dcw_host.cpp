@@ -2,6 +2,7 @@
 #include "dcw_host.h"
 #include "dcw_dzt_enc.h"
 #include "dcw_lz4_dec.h"
+#include "dcw_inflate_dec.h"
 #include "dcw_lz4_enc.h"
 
 #include <fcntl.h>
@@ -300,6 +301,20 @@ ParsedSst parse_sst(const uint8_t* data, size_t size) {
     dec.resize(ul);
     if (!lz4_dec(ib + hn, (uint32_t)idx_sz - hn, (uint8_t*)dec.data(), ul)) {
       r.error = "index lz4 corrupt";
+      return r;
+    }
+    ib = (const uint8_t*)dec.data();
+    idx_sz = ul;
+  } else if (type == 2) { // zlib: the serial form of the data blocks' decoder
+    uint32_t ul;
+    int hn = zlib_preamble(ib, (uint32_t)idx_sz, &ul);
+    if (hn < 0 || (ul >> 31) || (idx_sz >> 28)) {
+      r.error = "index zlib preamble";
+      return r;
+    }
+    dec.resize(ul);
+    if (!inflate_dec(ib + hn, (uint32_t)idx_sz - hn, (uint8_t*)dec.data(), ul)) {
+      r.error = "index zlib corrupt";
       return r;
     }
     ib = (const uint8_t*)dec.data();

@@ -5,6 +5,7 @@
 #pragma once
 #include "dcw_gpu.h"
 #include "dcw_lz4_dec.h"
+#include "dcw_inflate_dec.h" // zlib_preamble and the launcher of dcw_zlib.hip
 #define DCW_ZSTD_WAVE
 #include "dcw_zstd_dec.h"
 #include "dcw_zstd_dec_large.h" // kZLitStride and the launcher of dcw_zstd_large.hip
@@ -25,6 +26,7 @@ enum DevErr : uint32_t {
   DE_PLAN_WIDTH = 8,   // planned block exceeds the emit kernel's entry bound
   DE_LZ4 = 9,          // LZ4/LZ4HC input block: bad preamble or stream
   DE_ZSTD = 10,        // zstd input block: bad preamble or frame
+  DE_ZLIB = 11,        // zlib input block: bad preamble or deflate stream
 };
 
 // ------------------------------------------------------------------
@@ -77,6 +79,13 @@ __global__ void k_verify_usize(const uint8_t* __restrict__ blob,
       uint32_t ul;
       if (lz4_preamble(p, sz, &ul) < 0) {
         set_err(err_flag, DE_LZ4);
+        return;
+      }
+      usize[i] = ul;
+    } else if (type == 2) { // zlib: varint32 preamble
+      uint32_t ul;
+      if (zlib_preamble(p, sz, &ul) < 0) {
+        set_err(err_flag, DE_ZLIB);
         return;
       }
       usize[i] = ul;
@@ -282,7 +291,7 @@ __global__ __launch_bounds__(256) void k_decompress(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
-    } else if (btype[i] != 1) { // 4, 5: k_decompress_lz4's block; 7: k_decompress_zstd's
+    } else if (btype[i] != 1) { // 2: k_decompress_zlib's block; 4, 5: k_decompress_lz4's; 7: k_decompress_zstd's
     } else if (n <= DEC_MAX && usize[i] <= DEC_MAX) {
       // 16-byte staging: byte-granular copies issued ~5000 DS ops per
       // block per wave and saturated the CU's DS issue pipe that the 16
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(256) void k_decompress_v1(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
-    } else if (btype[i] != 1) { // 4, 5: k_decompress_lz4's block; 7: k_decompress_zstd's
+    } else if (btype[i] != 1) { // 2: k_decompress_zlib's block; 4, 5: k_decompress_lz4's; 7: k_decompress_zstd's
     } else if (usize[i] <= DEC_MAX) {
       if (lane == 0) {
         if (snappy_uncompress(src, n, L.out, usize[i]) != usize[i])
@@ -402,7 +411,7 @@ __global__ __launch_bounds__(256) void k_decompress_v2(
       }
       if (lane == 0)
         for (uint32_t t = n & ~15u; t < n; t++) dst[t] = src[t];
-    } else if (btype[i] != 1) { // 4, 5: k_decompress_lz4's block; 7: k_decompress_zstd's
+    } else if (btype[i] != 1) { // 2: k_decompress_zlib's block; 4, 5: k_decompress_lz4's; 7: k_decompress_zstd's
     } else if (lane == 0) {
       if (snappy_uncompress(src, n, dst, usize[i]) != usize[i])
         set_err(err_flag, DE_SNAPPY);

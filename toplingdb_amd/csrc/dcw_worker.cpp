@@ -462,7 +462,8 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
   const char* zlh = getenv("DCW_ZSTD_LARGE_HOST");
   const bool zstd_large_on_host = zstd_on_host || (zlh && atoi(zlh) != 0);
   // the same walk lists the LZ4 / LZ4HC blocks (types 4 and 5) for
-  // k_decompress_lz4; the rewrite below keeps block order and copies every
+  // k_decompress_lz4 and the zlib blocks (type 2) for k_decompress_zlib; the
+  // rewrite below keeps block order and copies every
   // block that is not host-only verbatim, so the indices hold either way
   for (size_t bi = 0; bi < L->gi.blocks.size(); bi++) {
     const BlockRef& blk = L->gi.blocks[bi];
@@ -487,6 +488,14 @@ int load_inputs(const dcw_job_desc* d, LoadedInputs* L, std::string* err,
       L->gi.lz4_blocks.push_back((uint32_t)bi);
       L->gi.lz4_stored_bytes += blk.size;
       DI.lz4.push_back(blk_dict[bi]);
+    } else if (type == 2) { // zlib: k_decompress_zlib's list
+      if (blk_dict[bi] != DictInputs::kNone) {
+        // inflateSetDictionary (util/compression.h Zlib_Uncompress) is not built
+        *err = "unsupported: zlib blocks with a preset dictionary";
+        return -1;
+      }
+      L->gi.zlib_blocks.push_back((uint32_t)bi);
+      L->gi.zlib_stored_bytes += blk.size;
     }
   }
   L->us_parse += now_usec() - tphase;
