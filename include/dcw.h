@@ -42,14 +42,16 @@ enum {
 enum {
   DCW_COMPRESSION_NONE = 0x0,
   DCW_COMPRESSION_SNAPPY = 0x1,
-  DCW_COMPRESSION_ZLIB = 0x2, /* INPUT blocks only: varint32 decompressed
+  DCW_COMPRESSION_ZLIB = 0x2, /* input and output: varint32 decompressed
                                  size + one raw deflate stream
-                                 (util/compression.h Zlib_Uncompress,
-                                 compress_format_version 2, window_bits
-                                 -14), decoded on the GPU
-                                 (k_decompress_zlib).  Refused: zlib as
-                                 output compression, and type-2 blocks in a
-                                 file with a preset dictionary */
+                                 (util/compression.h Zlib_Compress /
+                                 Zlib_Uncompress, compress_format_version 2,
+                                 window_bits -14).  Decoded on the GPU
+                                 (k_decompress_zlib) and encoded there
+                                 (k_compress_zlib, 16 KiB windows).  Refused:
+                                 zlib output together with
+                                 output_table_factory = 1, and type-2 blocks
+                                 in a file with a preset dictionary */
   DCW_COMPRESSION_ZSTD = 0x7, /* INPUT blocks only (util/compression.h:1332
                                  framing: varint32 decompressed size + zstd
                                  frame): decoded on the GPU when the frame

@@ -204,7 +204,7 @@ class DcwGpuCompactionExecutor : public CompactionExecutor {
     if (!p.compaction_filter_factory.clazz.empty())
       return Status::NotSupported("compaction filter");
     if (p.compression != kNoCompression && p.compression != kSnappyCompression &&
-        p.compression != kLZ4Compression && p.compression != kLZ4HCCompression)
+        p.compression != kZlibCompression && p.compression != kLZ4Compression && p.compression != kLZ4HCCompression)
       return Status::NotSupported("compression type");
 
     // input file path: cf_paths[path_id] + %06llu.sst (MakeTableFileName)
@@ -245,6 +245,7 @@ class DcwGpuCompactionExecutor : public CompactionExecutor {
     d->output_level = p.output_level;
     d->bottommost_level = p.bottommost_level ? 1 : 0;
     d->compression = p.compression == kSnappyCompression ? DCW_COMPRESSION_SNAPPY
+                     : p.compression == kZlibCompression ? DCW_COMPRESSION_ZLIB
                      : p.compression == kLZ4Compression  ? DCW_COMPRESSION_LZ4
                      : p.compression == kLZ4HCCompression
                          ? DCW_COMPRESSION_LZ4HC

@@ -278,6 +278,26 @@ class GpuJob {
   std::vector<RdFrag> rd_frags_;
 };
 
+// One planned output data block, as the emit, compress, checksum and pack
+// kernels see it.
+struct EmitBlockDesc {
+  uint32_t first;     // survivor index of first entry (relative to chunk base added on host)
+  uint32_t count;
+  uint32_t unc_size;  // total uncompressed block size (with restarts+footer)
+  uint32_t num_restarts;
+  uint64_t uout;      // offset into ucblob
+  uint64_t cout;      // offset of the block's compressed-output slot in cblob
+};
+
+#if defined(__HIPCC__)
+// dcw_zlib_enc.hip: k_compress_zlib, 4 blocks per work-group; the same
+// bsize/btype contract as the snappy and LZ4 compress kernels
+void launch_compress_zlib(uint32_t grid, hipStream_t stream,
+                          const EmitBlockDesc* bds, uint32_t nblocks,
+                          const uint8_t* ucblob, uint8_t* cblob, uint32_t* bsize,
+                          uint8_t* btype, uint32_t* err_flag, uint32_t err_code);
+#endif
+
 // device management
 int gpu_init(int device_ordinal, std::string* err);
 void gpu_shutdown();

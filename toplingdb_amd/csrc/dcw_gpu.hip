@@ -41,6 +41,7 @@
 #include "dcw_zstd_dict.h" // the launchers of dcw_dict.hip
 #include "dcw_k_merge.h"
 #include "dcw_k_emit.h"
+#include "dcw_deflate_enc.h" // slot sizes; the kernel is in dcw_zlib_enc.hip
 #include "dcw_k_filter_dzt.h"
 #include "dcw_k_dzt_in.h"
 
@@ -1565,7 +1566,7 @@ int GpuJob::emit_blocks(const std::vector<PlannedBlock>& blocks, const TableOpts
   uint64_t last = blocks.back().first + blocks.back().count;
   uint64_t nent = last - first;
   (void)nent;
-  // descs: raw-image offsets (uout) and, for snappy or LZ4 output, every
+  // descs: raw-image offsets (uout) and, for snappy, LZ4 or zlib output, every
   // block's own compressed-output slot (cout): a running sum of worst-case
   // encoder sizes, so one huge block does not size every slot of the chunk.
   // Snappy blocks over SNAP_MAX_UNC are listed for k_compress_large.
@@ -1597,6 +1598,15 @@ int GpuJob::emit_blocks(const std::vector<PlannedBlock>& blocks, const TableOpts
         return -1;
       }
       cslot += (5 + lz4_max_compressed(pb.unc_size) + 63) & ~(uint64_t)63;
+    } else if (o.compression == 2) {
+      if (pb.unc_size > kDeflMaxUnc) {
+        if (err)
+          *err = "data block of " + std::to_string(pb.unc_size) +
+                 " B is past the zlib encoder's 2 GiB bound; job outside "
+                 "envelope";
+        return -1;
+      }
+      cslot += (5 + deflate_max_compressed(pb.unc_size) + 63) & ~(uint64_t)63;
     }
   }
   p->emit_base = first;
@@ -1664,6 +1674,14 @@ int GpuJob::emit_blocks(const std::vector<PlannedBlock>& blocks, const TableOpts
                        dim3(256), 0, p->stream, p->d_bds, nb, p->d_ucblob,
                        p->d_cblob, p->d_ebsize, p->d_ebtype,
                        (uint8_t)o.compression, p->d_err);
+    p->kend();
+  } else if (o.compression == 2) {
+    HIPCHK(p->d_cblob.reserve(cslot));
+    p->kbegin("compress_zlib", 3.6 * (double)uout); // three read passes
+    uint32_t cgrid = (nb + 3) / 4;
+    launch_compress_zlib(cgrid < 4096 ? cgrid : 4096, p->stream, p->d_bds, nb,
+                         p->d_ucblob, p->d_cblob, p->d_ebsize, p->d_ebtype,
+                         p->d_err, DE_BLOCK_PARSE);
     p->kend();
   } else {
     hipLaunchKernelGGL(k_sizes_nocomp, dim3(grid_for(nb)), dim3(256), 0,

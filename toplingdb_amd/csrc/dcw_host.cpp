@@ -4,6 +4,7 @@
 #include "dcw_lz4_dec.h"
 #include "dcw_inflate_dec.h"
 #include "dcw_lz4_enc.h"
+#include "dcw_deflate_enc.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -485,6 +486,14 @@ SstIndexEntry append_block(std::string& out, const TableOpts& o,
       bn = cn;
       type = (uint8_t)o.compression;
     }
+  } else if (try_compress && o.compression == 2 && n > 0 && n <= kDeflMaxUnc) {
+    comp.resize(5 + deflate_max_compressed(n));
+    size_t cn = deflate_encode_block(data, (uint32_t)n, (uint8_t*)comp.data());
+    if (cn <= ((uint64_t)896 * n) >> 10) { // the same rule again
+      body = (const uint8_t*)comp.data();
+      bn = cn;
+      type = 2;
+    }
   }
   SstIndexEntry h{out.size(), bn};
   out.append((const char*)body, bn);
@@ -571,6 +580,7 @@ std::string build_tail(const TableOpts& o, const TailStats& st,
   adds("rocksdb.property.collectors", "[]");
   if (!o.cf_name.empty()) adds("rocksdb.column.family.name", o.cf_name);
   adds("rocksdb.compression", o.compression == 1   ? "Snappy"
+                              : o.compression == 2 ? "Zlib"
                               : o.compression == 4 ? "LZ4"
                               : o.compression == 5 ? "LZ4HC"
                                                    : "NoCompression");

@@ -58,14 +58,7 @@ __global__ void k_shared_prefix(const uint64_t* __restrict__ s_k0,
 // ------------------------------------------------------------------
 // emit / compress / checksum / pack
 // ------------------------------------------------------------------
-struct EmitBlockDesc {
-  uint32_t first;     // survivor index of first entry (relative to chunk base added on host)
-  uint32_t count;
-  uint32_t unc_size;  // total uncompressed block size (with restarts+footer)
-  uint32_t num_restarts;
-  uint64_t uout;      // offset into ucblob
-  uint64_t cout;      // offset of the block's compressed-output slot in cblob
-};
+// EmitBlockDesc: dcw_gpu.h (dcw_zlib_enc.hip reads it too)
 
 // one workgroup per block; thread 0 walks the block's entry sizes into an
 // LDS offset table (<=512 entries per 4 KiB-class block), then all threads

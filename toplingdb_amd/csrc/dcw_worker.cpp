@@ -644,21 +644,22 @@ int check_desc(const dcw_job_desc* d, dcw_job_result* res) {
   if (d->comparator_name &&
       strcmp(d->comparator_name, "leveldb.BytewiseComparator") != 0)
     return fail(res, 12, "unsupported comparator (bytewise only)");
-  if (d->compression != 0 && d->compression != 1 && d->compression != 4 &&
-      d->compression != 5)
+  if (d->compression != 0 && d->compression != 1 && d->compression != 2 &&
+      d->compression != 4 && d->compression != 5)
     return fail(res, 13,
-                "unsupported output compression (none, snappy, LZ4 or LZ4HC "
-                "only)");
+                "unsupported output compression (none, snappy, zlib, LZ4 or "
+                "LZ4HC only)");
   if (d->checksum_type != 0 && d->checksum_type != 1 && d->checksum_type != 4)
     return fail(res, 14,
                 "unsupported checksum_type (kNoChecksum/kCRC32c/kXXH3 only)");
   if (d->output_table_factory > 1)
     return fail(res, 14, "unsupported output_table_factory");
   // DcwZipTable value blocks have their own dictionary codec, which a
-  // non-zero compression switches on: LZ4 there would be stored as snappy
+  // non-zero compression switches on: zlib or LZ4 there would be stored as
+  // snappy
   if (d->output_table_factory == 1 && d->compression > 1)
     return fail(res, 13,
-                "unsupported: LZ4/LZ4HC output compression with "
+                "unsupported: zlib/LZ4/LZ4HC output compression with "
                 "output_table_factory = 1 (DcwZipTable)");
   return 0;
 }
